@@ -75,7 +75,32 @@ def parse():
     ap.add_argument("--force-process-group", action="store_true",
                     help="initialise torch.distributed even at world size 1, so that the RCCL all-gather path runs on one GPU")
     ap.add_argument("--no-chamfer-op", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(rank 0; float32/float64, at most 64 MB in all) so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array.  Every array has one row per pair; if together they exceed 64 MB, the
+    same fixed, seeded sample of rows is taken from each and its row numbers are written as sample_rows.npy."""
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    rows = next(iter(arrays.values())).shape[0]
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, max(1, rows * DUMP_LIMIT_BYTES // (2 * total)), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(points, kernel, iters, inst_iters_per_pair):
@@ -314,6 +339,7 @@ def bench_dcp(args, dev, world, rank):
         s, t, _ = synthetic.make_pairs(P, args.points, seed=2021, first_id=(b * world + rank) * P)
         batches.append((s.to(dev), t.to(dev)))
     losses = []
+    last = {}
 
     def step(b):
         s, t = batches[b]
@@ -322,6 +348,7 @@ def bench_dcp(args, dev, world, rank):
         with torch.no_grad():
             loss, min_1 = Predict_loss(moved, t)
         losses.append(float(loss.mean()))
+        last.update(T12=T12, loss=loss, min_1=min_1)
 
     def sync():
         if world > 1:
@@ -336,6 +363,8 @@ def bench_dcp(args, dev, world, rank):
         step(args.warmup + k)                    # the model replays each chunk's launches as one HIP graph (models/dcp.py)
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)          # before the extra step below runs the last batch again
     # kernel times for `roofline`: ONE more step, outside the timed region, launched eagerly with an event pair around every
     # houv_gemm_f32 / houv_attention_f32 call (events cannot be recorded inside a graph replay)
     n_timed = len(losses)
@@ -516,6 +545,9 @@ def main():
     mine = full[rank * P:(rank + 1) * P] if world > 1 else full
     r_err = rotation_error(mine[:, :3, :3], pose[:, :3, :3])
     t_err = translation_error(mine[:, :3, 3], pose[:, :3, 3])
+    if args.dump_outputs and rank == 0:
+        # solve_model's return (r_err, t_err, ans) for this rank's pairs of the last timed step (ICP-refined with --icp)
+        dump_outputs(args.dump_outputs, {"ans": mine, "rot_err_deg": r_err, "trans_err": t_err})
 
     # ---- dominant kernel: live HIP-event timing on the launch stream ----
     # the retry stages of a step run concurrently on side streams (solver.CONCURRENT_RETRIES): their launches overlap

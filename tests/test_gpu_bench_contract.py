@@ -29,9 +29,17 @@ def _run(argv, monkeypatch):
     return json.loads(lines[0])
 
 
-def test_bench_line_contract(monkeypatch):
+def test_bench_line_contract(monkeypatch, tmp_path):
     d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "8", "--points", "768", "--kernel", "26",
-              "--iters", "40", "--no-cpu-baseline", "--no-chamfer-op"], monkeypatch)
+              "--iters", "40", "--no-cpu-baseline", "--no-chamfer-op", "--dump-outputs", str(tmp_path)], monkeypatch)
+    # --dump-outputs: solve_model's (r_err, t_err, ans) of the last timed step, the arrays the quality figures come from
+    import numpy as np
+    ans, r_err, t_err = (np.load(tmp_path / f"{n}.npy") for n in ("ans", "rot_err_deg", "trans_err"))
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["ans.npy", "rot_err_deg.npy", "trans_err.npy"]
+    assert ans.shape == (8, 4, 4) and r_err.shape == (8,) and t_err.shape == (8,)
+    assert ans.dtype == r_err.dtype == t_err.dtype == np.float32 and not ans[:, 3].any()
+    assert abs(float(r_err.mean()) - d["quality"]["mean_rot_err_deg"]) < 1e-5 * max(1.0, float(r_err.mean()))
+    assert abs(float(t_err.mean()) - d["quality"]["mean_trans_err"]) < 1e-5 * max(1.0, float(t_err.mean()))
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                      ("config", dict), ("roofline", dict)):
