@@ -10,6 +10,24 @@ constexpr int kAccStride = 16;   // row stride (floats) of the per-wave reductio
 typedef float houv_f4v __attribute__((ext_vector_type(4)));
 typedef const houv_f4v __attribute__((address_space(3))) * lds_f4;   // LDS pointer usable from a 32-bit byte address
 
+// Per-lane global accesses of the fused loop go through buffer resources: a uniform base (4 SGPRs) + ONE 32-bit per-lane byte
+// offset shared by all of a lane's points + a uniform byte offset (the point's chunk k * BLOCK, the row of the workspace).  As
+// plain pointers, LLVM hoisted one 64-bit address per point and row out of the iteration loop and spilled them to scratch
+// (solve_kernel<512, 4, 4, 2, 1>: 124 of its 192 scratch reloads, 416 B per lane).  Every access is in bounds by construction
+// (callers guard with the same predicates as before); `bytes` is the size of the region.
+// The thread index, opaque to the optimiser at every use: whatever the fused loop derives from it per lane (offsets, LDS
+// addresses, lane masks) is recomputed where it is used, with a VALU instruction or two, instead of being hoisted out of the
+// iteration loop, where it lived in a VGPR (spilled to scratch) or an SGPR pair (spilled to VGPR lanes) for the whole loop.
+__device__ __forceinline__ int tid_x() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+typedef __amdgpu_buffer_rsrc_t buf_t;
+__device__ __forceinline__ buf_t make_buf(const void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, bytes, 0x00020000);   // raw, 32-bit data format
+}
+
 // ------------------------------------------------------------------------------------------------
 // The brute-force sweep: for each of this lane's Q queries, min over all references of the NMET
 // squared distances, plus the id of the 16-reference tracking unit (kTrk) that produced each minimum.
@@ -232,7 +250,7 @@ constexpr int kStampWgs = 4096;
 __device__ unsigned long long g_stamp_wg[kStampWgs * 24];
 #define HOUV_STAMP_ADD(i, v) atomicAdd(&g_stamp_wg[(blockIdx.x % kStampWgs) * 24 + (i)], (unsigned long long)(v))
 #define HOUV_PSTAT(i, v) HOUV_STAMP_ADD(16 + (i), v)
-#define HOUV_PSTAMP(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); if ((threadIdx.x & 63) == 0) HOUV_PSTAT(i, n_ - pst_); pst_ = n_; } while (0)
+#define HOUV_PSTAMP(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); if ((tid_x() & 63) == 0) HOUV_PSTAT(i, n_ - pst_); pst_ = n_; } while (0)
 #else
 #define HOUV_PSTAMP(i) do {} while (0)
 #endif
@@ -242,8 +260,15 @@ __device__ unsigned long long g_stamp_wg[kStampWgs * 24];
 template <int BLOCK, int Q, int OWN>
 __device__ __forceinline__ int pt_index(int k) {
   static_assert(OWN >= 1 && Q % OWN == 0 && kSub % OWN == 0, "ownership chunk must divide Q and the sub-tile");
-  return (k / OWN) * (BLOCK * OWN) + (int)threadIdx.x * OWN + (k % OWN);
+  return (k / OWN) * (BLOCK * OWN) + tid_x() * OWN + (k % OWN);
 }
+// the uniform part of pt_index (pt_index(k) = pt_base(k) + thread index * OWN): buffer accesses take it as a uniform offset
+template <int BLOCK, int Q, int OWN>
+constexpr int pt_base(int k) { return (k / OWN) * (BLOCK * OWN) + (k % OWN); }
+
+// Remembered nearest neighbours of the pruned search (nn_ws): per direction one record of 4 x int16 per query, the NN index of
+// metric m at int16 m, so that the bounds take ONE 8-byte load per query.  `dir_off` = byte offset of the direction's records.
+constexpr int kNnRec = 8;
 
 #ifndef HOUV_PRUNE_GROUP
 #define HOUV_PRUNE_GROUP 1
@@ -328,8 +353,7 @@ __device__ __forceinline__ void take_units(float ta, float tb, int unit0, float&
 template <int BLOCK, int Q, int NMET, int OWN, int L, int G>
 __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                             const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                            const short* __restrict__ prev, int prev_stride, int count,
-                                            unsigned long long (&un)[L]) {
+                                            buf_t ws, int prev_off, int count, unsigned long long (&un)[L]) {
 #ifdef HOUV_STAMPS
   unsigned long long pst_ = __builtin_readcyclecounter();
 #endif
@@ -337,14 +361,23 @@ __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, con
     float ub[Q][NMET];
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
-      const int i = pt_index<BLOCK, Q, OWN>(k);
-      const bool ok = i < count;
-      const int ii = ok ? i : 0;
-      { const float4 r = refs[prev[0 * prev_stride + ii]]; ub[k][0] = metric_sqdist<0>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      const bool ok = pt_index<BLOCK, Q, OWN>(k) < count;
+      // the query's record (a lane past the end of the cloud keeps index 0: its bounds are discarded below)
+      unsigned w0 = 0u, w1 = 0u;
+      const int voff = tid_x() * (OWN * kNnRec), soff = prev_off + pt_base<BLOCK, Q, OWN>(k) * kNnRec;
+      if (ok) {
+        if constexpr (NMET == 4) {
+          const auto r = __builtin_amdgcn_raw_buffer_load_b64(ws, voff, soff, 0);
+          w0 = r[0]; w1 = r[1];
+        } else {
+          w0 = __builtin_amdgcn_raw_buffer_load_b32(ws, voff, soff, 0);
+        }
+      }
+      { const float4 r = refs[w0 & 0xffffu]; ub[k][0] = metric_sqdist<0>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
       if constexpr (NMET == 4) {
-        { const float4 r = refs[prev[1 * prev_stride + ii]]; ub[k][1] = metric_sqdist<1>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
-        { const float4 r = refs[prev[2 * prev_stride + ii]]; ub[k][2] = metric_sqdist<2>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
-        { const float4 r = refs[prev[3 * prev_stride + ii]]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+        { const float4 r = refs[w0 >> 16]; ub[k][1] = metric_sqdist<1>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+        { const float4 r = refs[w1 & 0xffffu]; ub[k][2] = metric_sqdist<2>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+        { const float4 r = refs[w1 >> 16]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
       }
 #pragma unroll
       for (int m = 0; m < NMET; ++m) ub[k][m] = ok ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;   // box distances are rounded: stay conservative
@@ -398,7 +431,7 @@ __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, con
 template <int BLOCK, int Q, int NMET, int OWN>
 __device__ __forceinline__ void pruned_sweep(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                              const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                             const short* __restrict__ prev, int prev_stride, int count, int rot,
+                                             buf_t ws, int prev_off, int count, int rot,
                                              float (&best)[Q][NMET], int (&btile)[Q][NMET],
                                              unsigned long long* __restrict__ stats = nullptr, int cap_slack = -1) {
   // G queries share one sub-tile list and every gathered reference (G = 1 by default, see above); a lane's Q/G lists
@@ -409,7 +442,7 @@ __device__ __forceinline__ void pruned_sweep(const float4* __restrict__ refs, co
 #ifdef HOUV_STAMPS
   unsigned long long pst_ = __builtin_readcyclecounter();
 #endif
-  prune_masks<BLOCK, Q, NMET, OWN, L, G>(refs, boxes, ntile, qx, qy, qz, prev, prev_stride, count, un);
+  prune_masks<BLOCK, Q, NMET, OWN, L, G>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
 #pragma unroll
   for (int k = 0; k < Q; ++k)
 #pragma unroll
@@ -420,7 +453,7 @@ __device__ __forceinline__ void pruned_sweep(const float4* __restrict__ refs, co
 #pragma unroll
     for (int g = 0; g < L; ++g) asked += __popcll(un[g]);
     asked = wave_incl_scan_dpp(asked);
-    if ((threadIdx.x & 63) == 63) {
+    if ((tid_x() & 63) == 63) {
       atomicAdd(&stats[0], (unsigned long long)asked);
       atomicAdd(&stats[2], 1ull);
     }
@@ -443,7 +476,7 @@ __device__ __forceinline__ void pruned_sweep(const float4* __restrict__ refs, co
       uni_g += __popcll(u);
       all |= u;
     }
-    if ((threadIdx.x & 63) == 0) {
+    if ((tid_x() & 63) == 0) {
       HOUV_PSTAT(0, (unsigned long long)asked);           // sub-tile visits the wave's lanes asked for
       HOUV_PSTAT(2, 1ull);                                // waves
       HOUV_PSTAT(6, (unsigned long long)uni_g);           // sum over lists of the per-list wave unions
@@ -548,9 +581,9 @@ __device__ __forceinline__ void pruned_sweep(const float4* __restrict__ refs, co
           btile[g * G + k][m] = lt ? 2 * t + (lb ? 1 : 0) : btile[g * G + k][m];
         }
   }
-  if (stats && (threadIdx.x & 63) == 0) atomicAdd(&stats[1], (unsigned long long)nsteps);
+  if (stats && (tid_x() & 63) == 0) atomicAdd(&stats[1], (unsigned long long)nsteps);
 #ifdef HOUV_STAMPS
-  if ((threadIdx.x & 63) == 0) HOUV_PSTAT(1, steps_);
+  if ((tid_x() & 63) == 0) HOUV_PSTAT(1, steps_);
   HOUV_PSTAMP(5);
 #endif
 }
@@ -587,16 +620,16 @@ template <int BLOCK, int Q, int NMET, int TS = 0>
 __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                                     const float4* __restrict__ qarr, float4* wlo, float4* whi,
                                                     const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                                    const short* __restrict__ prev, int prev_stride, int count, int rot,
+                                                    buf_t ws, int prev_off, int count, int rot,
                                                     const SortedStage& st, float4* __restrict__ res, float (&best)[Q][NMET],
                                                     int (&btile)[Q][NMET], unsigned long long* __restrict__ stats) {
   static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "the bin prefix runs on one wave while another resets the block counter");
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = tid_x(), lane = tid & 63;
   unsigned long long un[Q];
-  prune_masks<BLOCK, Q, NMET, 1, Q, 1>(refs, boxes, ntile, qx, qy, qz, prev, prev_stride, count, un);
+  prune_masks<BLOCK, Q, NMET, 1, Q, 1>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
 #ifdef HOUV_STAMPS
   unsigned long long pst_ = __builtin_readcyclecounter();   // diagnostic build: [3] bounds, [4] box tests, [5] sort, [6] walk, [7] end barrier
-  if ((threadIdx.x & 63) == 0) HOUV_PSTAT(2, 1ull);
+  if ((tid_x() & 63) == 0) HOUV_PSTAT(2, 1ull);
 #endif
   int len[Q], rnk[Q];
 #pragma unroll
@@ -732,7 +765,7 @@ __device__ __forceinline__ void tile_boxes(const float (&x)[Q], const float (&y)
       hx = fmaxf(hx, __shfl_xor(hx, o, 64)); hy = fmaxf(hy, __shfl_xor(hy, o, 64)); hz = fmaxf(hz, __shfl_xor(hz, o, 64));
     }
     const int t = pt_index<BLOCK, Q, OWN>(c * OWN) / kTile;
-    if (((int)threadIdx.x % (kTile / OWN)) == 0 && t < ntile) {
+    if ((tid_x() % (kTile / OWN)) == 0 && t < ntile) {
       box[2 * t] = make_float4(lx, ly, lz, 0.f);
       box[2 * t + 1] = make_float4(hx, hy, hz, 0.f);
     }

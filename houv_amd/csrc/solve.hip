@@ -51,8 +51,9 @@ struct SolveArgs {
   float* out_T;
   float* out_grad;
   float* out_cd;
-  short* nn_ws;      // pruned mode, per hypothesis 16 rows of ws_stride int16: rows [dir*4 + metric] = index of each query's NN
-                     // in the last iteration; rows 8..15 = ws_stride float4 of scratch (the balanced walk's minima per query)
+  short* nn_ws;      // pruned mode, per hypothesis 16 rows of ws_stride int16 (16-byte aligned): rows 0..7 = ws_stride records of
+                     // 4 x int16 per direction (kNnRec; direction 0 first) = index of each query's NN per metric in the last
+                     // iteration; rows 8..15 = ws_stride float4 of scratch (the balanced walk's minima per query)
   int ws_valid;      //   1: nn_ws holds the NNs of the iteration before this launch's first one
   int ws_stride;
   int pred_mode;     // diagnostics (HOUV_SOLVE_PREDICT): 0 normal; 1 always predict direction B (every A-win takes the
@@ -70,7 +71,7 @@ struct SolveArgs {
 #define HOUV_STAMP(i)                                                        \
   do {                                                                       \
     const unsigned long long now_ = __builtin_readcyclecounter();           \
-    if ((threadIdx.x & 63) == 0) HOUV_STAMP_ADD(i, now_ - t_stamp_);   \
+    if ((tid_x() & 63) == 0) HOUV_STAMP_ADD(i, now_ - t_stamp_);   \
     t_stamp_ = now_;                                                         \
   } while (0)
 #define HOUV_STAMP_PARAM , unsigned long long& t_stamp_
@@ -150,6 +151,18 @@ __device__ inline Smem carve(unsigned char* base, int N, int M, int block, int n
   return s;
 }
 
+// A uniform value made opaque to the optimiser where the iteration loop uses it: what the loop derives from it in VALU
+// (conversions, quotients, LDS addresses) is recomputed there instead of being hoisted out of the loop into VGPRs that spilled.
+template <typename T>
+__device__ __forceinline__ T fresh(T v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+__device__ __forceinline__ const float* fresh_lds(const float* p) {
+  typedef const float __attribute__((address_space(3))) * lds_f;
+  return (const float*)(lds_f)(size_t)fresh((unsigned)(size_t)(lds_f)p);
+}
+
 __device__ __forceinline__ void store_pose(float* dst, const Pose& f) {
   const float* src = reinterpret_cast<const float*>(&f);
 #pragma unroll
@@ -174,7 +187,7 @@ template <int BLOCK, int Q>
 __device__ __forceinline__ void select_smallest(const unsigned (&key)[Q], int ksel, unsigned* hist, int* ctl,
                                                 bool (&sel)[Q], int& hrot) {
   constexpr int NW = BLOCK / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = tid_x(), lane = tid & 63, wave = tid >> 6;
   unsigned prefix = 0u, mask = 0u;
   int remaining = ksel, neq = 0;
 #pragma unroll
@@ -262,7 +275,7 @@ constexpr int kGradN = 12;
 // wave-level DPP sum; lane 63 parks the total
 __device__ __forceinline__ void park(float v, float* dst) {
   v = wave_sum_to_lane63(v);
-  if ((threadIdx.x & 63) == 63) *dst = v;
+  if ((tid_x() & 63) == 63) *dst = v;
 }
 
 // selections of one direction: bit k of bits[m] = query k of this lane takes part in metric m's mean
@@ -299,12 +312,14 @@ __device__ __forceinline__ float lane_sqrt_sum(const float (&bd)[Q], unsigned se
 }
 
 // this lane's share of G[3], GP[9] for one metric: exact NN recovery + products, per query (nothing is kept per query)
-template <int BLOCK, int Q, int MET, int DIR, int OWN>
+// WS: remember each query's NN for the pruned search's next bounds (metric MET's int16 of the query's record at ws + ws_off)
+template <int BLOCK, int Q, int MET, int DIR, int OWN, bool WS>
 __device__ __forceinline__ void lane_grad_sums(const Smem& sm, const float4* __restrict__ refs, const float (&qx)[Q],
                                                const float (&qy)[Q], const float (&qz)[Q], const float (&bd)[Q],
                                                const int (&bt)[Q], unsigned selbits, int count, const float (&px)[Q],
-                                               const float (&py)[Q], const float (&pz)[Q], float (&g)[kGradN], short* ws) {
-  const int rot = threadIdx.x & (kSub - 1);
+                                               const float (&py)[Q], const float (&pz)[Q], float (&g)[kGradN], buf_t ws,
+                                               int ws_off) {
+  const int rot = tid_x() & (kSub - 1);
 #pragma unroll
   for (int i = 0; i < kGradN; ++i) g[i] = 0.f;
   float R[9], T[3];
@@ -318,7 +333,9 @@ __device__ __forceinline__ void lane_grad_sums(const Smem& sm, const float4* __r
   for (int k = 0; k < Q; ++k) {
     int jn;
     const float4 nn = recover_nn<MET, kRescanBatch, true>(refs + bt[k] * kTrk, qx[k], qy[k], qz[k], bd[k], rot, jn);
-    if (ws && pt_index<BLOCK, Q, OWN>(k) < count) ws[pt_index<BLOCK, Q, OWN>(k)] = (short)(bt[k] * kTrk + jn);
+    if (WS && pt_index<BLOCK, Q, OWN>(k) < count)
+      __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(bt[k] * kTrk + jn), ws, tid_x() * (OWN * kNnRec),
+                                            ws_off + pt_base<BLOCK, Q, OWN>(k) * kNnRec + MET * 2, 0);
     if ((selbits >> k) & 1u) {
       const float s = (bd[k] < INFINITY) ? sqrtf(bd[k]) : NAN;
       const float inv = 1.0f / s;   // d == 0 -> inf, and 0*inf = NaN below, as torch's sqrt backward gives
@@ -358,12 +375,12 @@ __device__ __forceinline__ void park_sqrt_sums(const float (&best)[Q][NMET], con
 }
 
 // G, GP of the metrics in `mask` of one direction -> red[dir][wave][m*13 + 1 ..]; no barrier in here
-template <int BLOCK, int Q, int NMET, int DIR, int OWN>
+template <int BLOCK, int Q, int NMET, int DIR, int OWN, bool WS>
 __device__ __forceinline__ void park_grad_sums(const Smem& sm, const float4* __restrict__ refs, const float (&qx)[Q],
                                                const float (&qy)[Q], const float (&qz)[Q], const float (&best)[Q][NMET],
                                                const int (&btile)[Q][NMET], const unsigned (&selbits)[NMET], unsigned mask,
                                                int count, const float (&px)[Q], const float (&py)[Q], const float (&pz)[Q],
-                                               float* red_wave, short* ws, int ws_stride) {
+                                               float* red_wave, buf_t ws, int ws_off) {
   float bd[Q], g[kGradN];
   int bt[Q];
 #define HOUV_GRAD(MET)                                                                                              \
@@ -372,8 +389,8 @@ __device__ __forceinline__ void park_grad_sums(const Smem& sm, const float4* __r
       bd[k] = best[k][MET];                                                                                         \
       bt[k] = btile[k][MET];                                                                                        \
     }                                                                                                               \
-    lane_grad_sums<BLOCK, Q, MET, DIR, OWN>(sm, refs, qx, qy, qz, bd, bt, selbits[MET], count, px, py, pz, g,       \
-                                            ws ? ws + (size_t)MET * ws_stride : nullptr);                           \
+    lane_grad_sums<BLOCK, Q, MET, DIR, OWN, WS>(sm, refs, qx, qy, qz, bd, bt, selbits[MET], count, px, py, pz, g,   \
+                                                ws, ws_off);                                                        \
     _Pragma("unroll") for (int i = 0; i < kGradN; ++i) park(g[i], red_wave + MET * kAccN + 1 + i);                  \
   }
   HOUV_GRAD(0)
@@ -389,7 +406,7 @@ __device__ __forceinline__ void park_grad_sums(const Smem& sm, const float4* __r
 template <int BLOCK, int NMET>
 __device__ __forceinline__ void final_sums(const Smem& sm, int dir, bool want_s, unsigned grad_mask) {
   constexpr int NW = BLOCK / 64;
-  const int tid = threadIdx.x;
+  const int tid = tid_x();
   if (tid < NMET * kAccN) {
     const int m = tid / kAccN, i = tid % kAccN;
     if ((i == 0) ? want_s : (((grad_mask >> m) & 1u) != 0u)) {
@@ -416,11 +433,21 @@ __device__ __forceinline__ unsigned picked_direction(const Smem& sm, int k_full,
   return pick;
 }
 
+// this lane's source point k (pt_index) of the pair's cloud `src` (N points): one buffer_load_dwordx3; 0 past the end
+template <int BLOCK, int Q, int OWN>
+__device__ __forceinline__ void load_src_point(buf_t src, int k, int N, float& x, float& y, float& z) {
+  x = y = z = 0.f;
+  if (pt_index<BLOCK, Q, OWN>(k) < N) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b96(src, tid_x() * (OWN * 12), pt_base<BLOCK, Q, OWN>(k) * 12, 0);
+    x = __uint_as_float(v[0]); y = __uint_as_float(v[1]); z = __uint_as_float(v[2]);
+  }
+}
+
 // Mis-prediction repair (rare): metric MET's gradient flows through direction A, but A's rescans were skipped because the
 // previous iteration's winner was B and A's sweep state is gone.  Redo A for this one metric: moved points, single-metric
 // sweep (bit-identical minima and sub-tiles: same expression tree, same tie rule), selection, rescan, sums.
 template <int BLOCK, int Q, int MET, int OWN>
-__device__ __forceinline__ void repair_direction_a(const Smem& sm, const float* __restrict__ src, int N, int mpad, int k_sel,
+__device__ __forceinline__ void repair_direction_a(const Smem& sm, buf_t src, int N, int mpad, int k_sel,
                                                    int& hrot, float* red_wave) {
   float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
   float R[9], T[3];
@@ -430,11 +457,7 @@ __device__ __forceinline__ void repair_direction_a(const Smem& sm, const float* 
   for (int i = 0; i < 3; ++i) T[i] = sm.pose[9 + i];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int i = pt_index<BLOCK, Q, OWN>(k);
-    const bool ok = i < N;
-    sx[k] = ok ? src[i * 3 + 0] : 0.f;
-    sy[k] = ok ? src[i * 3 + 1] : 0.f;
-    sz[k] = ok ? src[i * 3 + 2] : 0.f;
+    load_src_point<BLOCK, Q, OWN>(src, k, N, sx[k], sy[k], sz[k]);
     mx[k] = __builtin_fmaf(sz[k], R[2], __builtin_fmaf(sy[k], R[1], sx[k] * R[0])) + T[0];
     my[k] = __builtin_fmaf(sz[k], R[5], __builtin_fmaf(sy[k], R[4], sx[k] * R[3])) + T[1];
     mz[k] = __builtin_fmaf(sz[k], R[8], __builtin_fmaf(sy[k], R[7], sx[k] * R[6])) + T[2];
@@ -453,7 +476,7 @@ __device__ __forceinline__ void repair_direction_a(const Smem& sm, const float* 
 #pragma unroll
   for (int k = 0; k < Q; ++k) bits |= sel[k] ? (1u << k) : 0u;
   float g[kGradN];
-  lane_grad_sums<BLOCK, Q, MET, 1, OWN>(sm, sm.tgt, mx, my, mz, bd, bt, bits, N, sx, sy, sz, g, nullptr);
+  lane_grad_sums<BLOCK, Q, MET, 1, OWN, false>(sm, sm.tgt, mx, my, mz, bd, bt, bits, N, sx, sy, sz, g, src, 0);
 #pragma unroll
   for (int i = 0; i < kGradN; ++i) park(g[i], red_wave + MET * kAccN + 1 + i);
 }
@@ -470,14 +493,14 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   extern __shared__ __attribute__((aligned(512))) unsigned char smem_raw[];   // 512 B: pruned_sweep's XOR-rotated gathers
   const int N = a.N, M = a.M;
   const Smem sm = carve(smem_raw, N, M, BLOCK, PRUNE >= 2 ? BLOCK * Q : 0, kPad);
-  const int tid = threadIdx.x;
+  const int tid = tid_x();
   const int ninst = a.P * a.K;
   // XCD-aware placement: workgroups b and b+8 share an XCD (and its L2), so give each XCD a contiguous
   // range of hypotheses -> the K restarts of one pair read the pair's clouds through ONE L2.
   int inst = blockIdx.x;
   if ((ninst & 7) == 0) inst = (blockIdx.x & 7) * (ninst >> 3) + (blockIdx.x >> 3);
   const int pair = inst / a.K;
-  const float* __restrict__ src = a.src + (size_t)pair * N * 3;
+  const buf_t src = make_buf(a.src + (size_t)pair * N * 3, N * 12);
   const float* __restrict__ tgt = a.tgt + (size_t)pair * M * 3;
   const int npad = (N + kPad - 1) / kPad * kPad, mpad = (M + kPad - 1) / kPad * kPad;
   const float4 pad4 = make_float4(INFINITY, INFINITY, INFINITY, 0.f);   // padding references never win
@@ -492,12 +515,13 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   int hrot = 0;
   __syncthreads();
   const int rot = tid & (kSub - 1);
-  short* ws_a = nullptr;   // NN of the moved points in the target (direction 1)
-  short* ws_b = nullptr;   // NN of the target points in the moved cloud (direction 0)
-  float4* ws_res = nullptr;   // balanced walk: per-query minima on their way back to the owning lanes
+  // this hypothesis' workspace (pruned mode; brute force: src again, never accessed): byte offsets of the NN records of
+  // direction 0 (NN of the target points in the moved cloud) and direction 1 (NN of the moved points in the target)
+  buf_t ws = src;
+  const int ws_b = 0, ws_a = a.ws_stride * kNnRec;
+  float4* ws_res = nullptr;   // balanced walk: per-query minima on their way back to the owning lanes (rows 8..15)
   if constexpr (PRUNE) {
-    ws_b = a.nn_ws + ((size_t)inst * 16 + 0) * a.ws_stride;
-    ws_a = a.nn_ws + ((size_t)inst * 16 + 4) * a.ws_stride;
+    ws = make_buf(a.nn_ws + (size_t)inst * 16 * a.ws_stride, 32 * a.ws_stride);
     ws_res = reinterpret_cast<float4*>(a.nn_ws + ((size_t)inst * 16 + 8) * a.ws_stride);
     float tx0[Q], ty0[Q], tz0[Q];
 #pragma unroll
@@ -558,17 +582,16 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       // ---- move this lane's source points, publish them as references for sweep B ----
       float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
       float R[9], T[3];
+      const float* pose = fresh_lds(sm.pose);
 #pragma unroll
-      for (int i = 0; i < 9; ++i) R[i] = sm.pose[i];
+      for (int i = 0; i < 9; ++i) R[i] = pose[i];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) T[i] = sm.pose[9 + i];
+      for (int i = 0; i < 3; ++i) T[i] = pose[9 + i];
 #pragma unroll
       for (int k = 0; k < Q; ++k) {
         const int i = pt_index<BLOCK, Q, OWN>(k);
         const bool ok = i < N;
-        sx[k] = ok ? src[i * 3 + 0] : 0.f;
-        sy[k] = ok ? src[i * 3 + 1] : 0.f;
-        sz[k] = ok ? src[i * 3 + 2] : 0.f;
+        load_src_point<BLOCK, Q, OWN>(src, k, N, sx[k], sy[k], sz[k]);
         // src @ R^T + T (houv.py:102)
         mx[k] = __builtin_fmaf(sz[k], R[2], __builtin_fmaf(sy[k], R[1], sx[k] * R[0])) + T[0];
         my[k] = __builtin_fmaf(sz[k], R[5], __builtin_fmaf(sy[k], R[4], sx[k] * R[3])) + T[1];
@@ -585,10 +608,10 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       }
       if (pruned_now) {
         if constexpr (PRUNE >= 2) {
-          pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws_a, a.ws_stride, N,
+          pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
                                               rot, sm.st, ws_res, best, btile, a.stats);
         } else if constexpr (PRUNE == 1) {
-          pruned_sweep<BLOCK, Q, NMET, OWN>(sm.tgt, sm.tbox, mpad / kSub, mx, my, mz, ws_a, a.ws_stride, N, rot, best, btile, a.stats, a.cap_slack);
+          pruned_sweep<BLOCK, Q, NMET, OWN>(sm.tgt, sm.tbox, mpad / kSub, mx, my, mz, ws, ws_a, N, rot, best, btile, a.stats, a.cap_slack);
         }
       } else {
         sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
@@ -600,8 +623,8 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       select_all<BLOCK, Q, NMET, OWN>(sm, best, N, a.k_full, a.k_view, hrot, sel);
       HOUV_STAMP(9);
       park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_a);
-      park_grad_sums<BLOCK, Q, NMET, 1, OWN>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws_a,
-                                            a.ws_stride);
+      park_grad_sums<BLOCK, Q, NMET, 1, OWN, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
+                                                        ws_a);
       HOUV_STAMP(8);
       __syncthreads();
       final_sums<BLOCK, NMET>(sm, 1, true, grad_a);
@@ -620,10 +643,10 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       const bool pruned_now = (PRUNE != 0) && ((a.ws_valid != 0) || (it > 0));
       if (pruned_now) {
         if constexpr (PRUNE >= 2) {
-          pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws_b, a.ws_stride, M,
+          pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
                                               rot, sm.st, ws_res, best, btile, a.stats);
         } else if constexpr (PRUNE == 1) {
-          pruned_sweep<BLOCK, Q, NMET, OWN>(sm.mov, sm.mbox, npad / kSub, tx, ty, tz, ws_b, a.ws_stride, M, rot, best, btile, a.stats, a.cap_slack);
+          pruned_sweep<BLOCK, Q, NMET, OWN>(sm.mov, sm.mbox, npad / kSub, tx, ty, tz, ws, ws_b, M, rot, best, btile, a.stats, a.cap_slack);
         }
       } else {
         sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
@@ -638,10 +661,10 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       __syncthreads();
       final_sums<BLOCK, NMET>(sm, 0, true, 0u);
       __syncthreads();
-      pick_a = picked_direction<NMET>(sm, a.k_full, a.k_view);
+      pick_a = picked_direction<NMET>(sm, fresh(a.k_full), fresh(a.k_view));
       const unsigned grad_b = allgrad ? kAllMet : (~pick_a & kAllMet);
-      park_grad_sums<BLOCK, Q, NMET, 0, OWN>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws_b,
-                                            a.ws_stride);
+      park_grad_sums<BLOCK, Q, NMET, 0, OWN, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
+                                                        ws_b);
       HOUV_STAMP(8);
       // ---- repair: won by A, but A's rescans were skipped ----
       const unsigned miss = pick_a & ~grad_a & kAllMet;
@@ -673,11 +696,15 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     // ---- per-hypothesis scalar tail: loss, closed-form gradient, Adam, next pose ----
     if (kAdamTid != 0 && tid == kAdamTid && it + 1 < a.n_iters) {   // next iteration's Adam scalars, while thread 0 works below
       const int step = a.steps_done + it + 2;
-      const AdamScalars asc = adam_scalars(step, a.lr, a.beta1, a.beta2);
+      const AdamScalars asc = adam_scalars(step, fresh(a.lr), fresh(a.beta1), fresh(a.beta2));
       sm.adam[(step & 1) * 2 + 0] = asc.step_size;
       sm.adam[(step & 1) * 2 + 1] = asc.bc2_sqrt;
     }
     if (tid == 0) {
+      const int k_full = fresh(a.k_full), k_view = fresh(a.k_view);
+      const float loss_scale = fresh(a.loss_scale);
+      const double lr = fresh(a.lr), beta1 = fresh(a.beta1), beta2 = fresh(a.beta2), eps = fresh(a.eps);
+      const int angle_base = fresh(a.angle_base), trans_mode = fresh(a.trans_mode);
       float p[8];
       Pose f;
       load_pose(f, sm.pose);        // the forward of the current parameters, kept from the end of the previous tail / the prologue
@@ -688,14 +715,14 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       bool bad = false;
 #pragma unroll
       for (int m = 0; m < NMET; ++m) {
-        const float kk = (float)((m == 0) ? a.k_full : a.k_view);
+        const float kk = (float)((m == 0) ? k_full : k_view);
         cd[m][0] = sm.acc[(m * 2 + 0) * kAccStride] / kk;   // over target points   (calc_cd_percent's 1st output)
         cd[m][1] = sm.acc[(m * 2 + 1) * kAccStride] / kk;   // over moved points    (2nd output)
         // torch.min(cat([first, second])): first wins ties; NaN propagates
         pick[m] = (cd[m][0] <= cd[m][1]) ? 0 : 1;
         val[m] = cd[m][pick[m]];
         if (cd[m][0] != cd[m][0] || cd[m][1] != cd[m][1]) { val[m] = NAN; bad = true; }
-        const float w = ((m == 0) ? 6.0f : 1.0f) * a.loss_scale / kk;
+        const float w = ((m == 0) ? 6.0f : 1.0f) * loss_scale / kk;
         const float* ac = sm.acc + (m * 2 + pick[m]) * kAccStride;
 #pragma unroll
         for (int i = 0; i < 3; ++i) gT[i] += w * ac[1 + i];
@@ -711,7 +738,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         for (int i = 0; i < 9; ++i) Mm[i] = NAN;
       }
       float g[8];
-      pose_backward(f, a.trans_mode, gT, Mm, g);
+      pose_backward(f, trans_mode, gT, Mm, g);
       if (it == a.n_iters - 1) {
         // outputs of the LAST forward (houv.py:134-136: the final step is never observed)
         if (a.out_score) a.out_score[inst] = val[0];
@@ -730,20 +757,20 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       const AdamScalars asc{sm.adam[(step & 1) * 2 + 0], sm.adam[(step & 1) * 2 + 1]};
       if (a.f64_params) {
         for (int k = 0; k < 8; ++k)
-          adam_step<double>(sm.state[k], sm.state[8 + k], sm.state[16 + k], (double)g[k], asc, a.beta1, a.beta2, a.eps);
+          adam_step<double>(sm.state[k], sm.state[8 + k], sm.state[16 + k], (double)g[k], asc, beta1, beta2, eps);
       } else {
         for (int k = 0; k < 8; ++k) {
           float pp = (float)sm.state[k], mm = (float)sm.state[8 + k], vv = (float)sm.state[16 + k];
-          adam_step<float>(pp, mm, vv, g[k], asc, a.beta1, a.beta2, a.eps);
+          adam_step<float>(pp, mm, vv, g[k], asc, beta1, beta2, eps);
           sm.state[k] = pp; sm.state[8 + k] = mm; sm.state[16 + k] = vv;
         }
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) p[k] = (float)sm.state[k];
-      pose_forward(p, a.angle_base, a.trans_mode, f);
+      pose_forward(p, angle_base, trans_mode, f);
       store_pose(sm.pose, f);
       if (kAdamTid == 0 && it + 1 < a.n_iters) {                       // single-wave workgroups: no other wave to do it
-        const AdamScalars nxt = adam_scalars(step + 1, a.lr, a.beta1, a.beta2);
+        const AdamScalars nxt = adam_scalars(step + 1, lr, beta1, beta2);
         sm.adam[((step + 1) & 1) * 2 + 0] = nxt.step_size;
         sm.adam[((step + 1) & 1) * 2 + 1] = nxt.bc2_sqrt;
       }
@@ -751,7 +778,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     __syncthreads();
     HOUV_STAMP(6);
   }
-  if (tid < 24) a.state[(size_t)inst * 24 + tid] = sm.state[tid];
+  if (tid_x() < 24) a.state[(size_t)inst * 24 + tid_x()] = sm.state[tid_x()];   // (the prologue's address is not kept alive)
   if (a.stats) {
     const unsigned long long dc = __builtin_amdgcn_s_memtime() - clk0, dr = __builtin_amdgcn_s_memrealtime() - rt0;
     if (tid == 0) {
@@ -891,6 +918,11 @@ static int solve_dispatch(const float* src, const float* tgt, int P, int N, int 
   if (!houv_solve_variant(N, M, prune ? 1 : 0, &block, &q, &mode)) return 0;
   if (prune && (!nn_ws || ws_stride < mx || (ws_stride & 7))) {
     set_error("%s: pruned mode needs a workspace of 16 x ws_stride int16 per hypothesis, ws_stride >= max(N,M) and a multiple of 8", who);
+    return 0;
+  }
+  // the kernel reads a query's NN record as one 8-byte load and its minima record as one 16-byte load
+  if (prune && ((uintptr_t)nn_ws & 15)) {
+    set_error("%s: the pruned-mode workspace must be 16-byte aligned", who);
     return 0;
   }
   if (prune && ws_valid < 0) {   // test aid: the pruned entry point with the search switched off = the brute-force kernel of this size

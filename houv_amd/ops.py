@@ -132,7 +132,8 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
 
 def solve_workspace(n_hypotheses, N, M, device):
     """Workspace of houv_solve_iterate_pruned for n hypotheses on clouds of N and M points: int16 [n, 16, stride] (rows 0..7
-    the remembered nearest neighbours per direction and metric, rows 8..15 scratch), stride = max(N, M) rounded up to 8."""
+    the remembered nearest neighbours, one 4 x int16 record per point and direction; rows 8..15 scratch), stride = max(N, M)
+    rounded up to 8.  The library needs the base 16-byte aligned (a fresh allocation is)."""
     stride = (max(int(N), int(M)) + 7) // 8 * 8
     return torch.empty((int(n_hypotheses), 16, stride), dtype=torch.int16, device=device)
 

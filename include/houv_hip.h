@@ -108,9 +108,9 @@ int houv_solve_iterate(const float* src, const float* tgt, int P, int N, int M, 
  * attained upper bound, and 32-point sub-tiles whose bounding box lies farther than the bound for all metrics are
  * skipped.  Works best on spatially sorted clouds (houv_amd.solver reorders them so that runs of 32 points are k-d-tree leaves).  The search result
  * and the summation order are those of houv_solve_iterate: same outputs BIT FOR BIT when given the same clouds.
- *   nn_ws[P*K, 16, ws_stride] int16  workspace, in/out, opaque to the caller: per hypothesis rows [dir*4 + metric] hold the
- *              previous nearest-neighbour index of every point, rows 8..15 are scratch (ws_stride x 16 bytes);
- *              ws_stride >= max(N, M) and a multiple of 8
+ *   nn_ws[P*K, 16, ws_stride] int16  workspace, in/out, opaque to the caller: per hypothesis rows 0..7 hold the previous
+ *              nearest-neighbour indices of every point (one 4 x int16 record per point and direction), rows 8..15 are
+ *              scratch (ws_stride x 16 bytes); ws_stride >= max(N, M) and a multiple of 8; nn_ws 16-byte aligned
  *   ws_valid   0: nn_ws holds nothing yet (the first iteration of this call runs the brute-force sweep)
  *              1: nn_ws was left by the previous call on the same hypotheses (chunked launches)
  *             -1: verification mode: every iteration runs the brute-force sweep (nn_ws is not used)
