@@ -158,6 +158,28 @@ def solve_iterate(src, tgt, state, K, *, steps_done, n_iters, angle_base, trans_
     return out
 
 
+KD_RULES = {"area": 0, "extent": 1}
+
+
+def kd_sort(cloud, leaf=32, rule="area", return_order=False):
+    """houv_kd_sort: cloud[P,N,3] fp32 (N <= 4096) reordered into the k-d leaf order of ``solver.kd_sort(cloud, leaf, rule)``, bit for
+    bit.  Returns the sorted cloud, and with ``return_order`` also order[P,N] int32 (input index of each output point)."""
+    _lib.require_gpu(cloud)
+    _want(cloud, _F32, "cloud")
+    if cloud.dim() != 3 or cloud.shape[2] != 3:
+        raise _lib.HouvHipError("kd_sort: expected cloud[P,N,3]")
+    if rule not in KD_RULES:
+        raise _lib.HouvHipError(f"kd_sort: rule must be one of {sorted(KD_RULES)}, got {rule!r}")
+    P, N, _ = cloud.shape
+    out = torch.empty_like(cloud)
+    order = torch.empty((P, N), dtype=_I32, device=cloud.device) if return_order else None
+    with torch.cuda.device(cloud.device):
+        ok = _lib.load().houv_kd_sort(_lib.ptr(cloud), P, N, int(leaf), KD_RULES[rule], _lib.ptr(out), _lib.ptr(order),
+                                      _lib.stream_of(cloud))
+    _lib.check(ok, "houv_kd_sort")
+    return (out, order) if return_order else out
+
+
 def icp_refine(src, tgt, init=None, max_correspondence_distance=0.02, max_iteration=500, relative_fitness=1e-6,
                relative_rmse=1e-6):
     """Batched point-to-point ICP (houv_icp_refine; Open3D registration_icp semantics, train_ICP.py:148-151).
@@ -212,6 +234,7 @@ def register_torch_ops():
     lib.define("icp_refine(Tensor src, Tensor tgt, Tensor? init, float max_correspondence_distance, int max_iteration, "
                "float relative_fitness, float relative_rmse) -> (Tensor, Tensor, Tensor, Tensor)")
     lib.define("pose_forward(Tensor params, int angle_base, int trans_mode, Tensor? src) -> (Tensor, Tensor, Tensor)")
+    lib.define("kd_sort(Tensor cloud, int leaf, str rule) -> (Tensor, Tensor)")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
     lib.impl("kabsch", kabsch, "CUDA")
@@ -227,6 +250,10 @@ def register_torch_ops():
         return (r[0], r[1], r[2] if src is not None else params.new_empty((0,)))
     lib.impl("icp_refine", _icp, "CUDA")
     lib.impl("pose_forward", _pose, "CUDA")
+
+    def _kd_sort(cloud, leaf, rule):
+        return kd_sort(cloud, leaf, rule, return_order=True)
+    lib.impl("kd_sort", _kd_sort, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

@@ -159,6 +159,18 @@ def kd_sort(cloud, leaf=32, rule=None):
 
 
 SPATIAL_SORT = "kd"          # "kd" (balanced k-d leaves, round 3) | "morton" (rounds 1-2)
+# who computes the "kd" order of a GPU tensor of up to 4096 points: "hip" = one houv_kd_sort launch (ops.kd_sort, the same
+# permutation bit for bit) | "torch" = kd_sort above; HOUV_KD_SORT selects it for A/B runs.  CPU tensors, Morton and larger clouds
+# always take the torch code.
+KD_SORT_IMPL = os.environ.get("HOUV_KD_SORT", "hip").strip().lower()
+KD_SORT_HIP_MAX_POINTS = 4096
+
+
+def _kd_sort_on_device(cloud):
+    """Whether spatial_sort hands ``cloud`` to the HIP k-d sort."""
+    return (KD_SORT_IMPL == "hip" and SPATIAL_SORT == "kd" and KD_RULE in ops.KD_RULES and cloud.is_cuda
+            and cloud.dtype == torch.float32 and cloud.dim() == 3 and cloud.shape[2] == 3
+            and 1 <= cloud.shape[1] <= KD_SORT_HIP_MAX_POINTS)
 
 
 _SORTED = {}                 # data_ptr -> (version, shape, device, order, leaf, weakref) of tensors spatial_sort itself produced
@@ -168,10 +180,14 @@ def spatial_sort(cloud, leaf=32):
     """The point order the pruned search wants (spatially compact 32-point sub-tiles; ``leaf`` = 64 for clouds of more than 2048
     points, whose visit masks are over 64-point super-tiles).  A tensor this function returned is
     recognised (the same tensor object: address, version counter, shape, weak reference) and handed back as it is: callers that keep their clouds sorted (bench.py,
-    the drivers' batches) do not pay for the sort again in every stage."""
+    the drivers' batches) do not pay for the sort again in every stage.  A GPU cloud of up to 4096 points is k-d sorted by one
+    houv_kd_sort launch (KD_SORT_IMPL), which returns the bits kd_sort returns."""
     if _sorted_leaf(cloud) == leaf:
         return cloud
-    out = kd_sort(cloud, leaf) if SPATIAL_SORT == "kd" else morton_sort(cloud)
+    if _kd_sort_on_device(cloud):
+        out = ops.kd_sort(cloud.contiguous(), leaf, KD_RULE)
+    else:
+        out = kd_sort(cloud, leaf) if SPATIAL_SORT == "kd" else morton_sort(cloud)
     _mark_sorted(out, leaf)
     return out
 

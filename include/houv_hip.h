@@ -135,6 +135,18 @@ int houv_solve_iterate_pruned(const float* src, const float* tgt, int P, int N, 
  * the test-suite can prove that every variant is compared with the CPU oracle. */
 int houv_solve_variant(int N, int M, int pruned, int* block, int* points_per_lane, int* prune_mode);
 
+/* The point order houv_solve_iterate_pruned wants, on the device: every cloud reordered so that consecutive runs of `leaf` points
+ * are the leaves of a balanced k-d tree -- bit for bit the permutation of houv_amd.solver.kd_sort (torch) on the same device.
+ * Lexicographic (x, y, z) start; then, level by level, every range of more than one tile (tiles = ceil(len / leaf)) is cut at
+ * a + (tiles - tiles/2) * leaf and stably reordered along one axis.  rule 0 = "area": the axis whose halves have the smallest
+ * summed projected box areas (axis 0 unless a later one is strictly smaller); 1 = "extent": the first axis of the largest
+ * max - min.  Floats order as torch's stable GPU sort does: -0 == +0, a NaN by its bits (positive above +Inf, negative below -Inf).
+ * Use leaf 32 when max(N, M) <= 2048 and 64 above (houv_amd.solver.sort_leaf), for both clouds, then call the pruned solve.
+ *   xyz[P,N,3] -> out[P,N,3] in that order; order_or_null[P,N] int32 = source index of each output point.
+ * 1 <= N <= 4096, leaf >= 1, P >= 0; out (and order) must not overlap xyz.  One workgroup per cloud.
+ * No counterpart in the reference (its solve takes the clouds as they come). */
+int houv_kd_sort(const float* xyz, int P, int N, int leaf, int rule, float* out, int32_t* order_or_null, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Point-to-point ICP refinement, one pair per workgroup (BASELINE configs[3]).
  * Replaces: the per-pair Open3D call of registration/train_ICP.py:137-153
