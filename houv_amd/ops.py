@@ -95,10 +95,11 @@ def pose_forward(params, angle_base, trans_mode=0, src=None):
 
 def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                       k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad=None,
-                      out_cd=None, nn_ws=None, ws_valid=0):
+                      out_cd=None, nn_ws=None, ws_valid=0, large=False):
     """The C-ABI call itself, caller-allocated outputs (``houv_solve_iterate`` / ``houv_solve_iterate_pruned`` when a
-    workspace is given): what ``torch.ops.houv.solve_iterate[_pruned]`` bind.  ``state`` [P*K,24] fp64 (and ``nn_ws``) are
-    updated in place; the out_* tensors receive the LAST forward's values.  Returns 1."""
+    workspace is given / ``houv_solve_iterate_large`` with ``large``): what ``torch.ops.houv.solve_iterate[_pruned|_large]``
+    bind.  ``state`` [P*K,24] fp64 (and ``nn_ws``) are updated in place; the out_* tensors receive the LAST forward's values.
+    Returns 1."""
     _lib.require_gpu(src, tgt, state, out_score, out_loss, out_R, out_T, out_grad, out_cd, nn_ws)
     _want(src, _F32, "src"); _want(tgt, _F32, "tgt"); _want(state, _F64, "state")
     P, N, _ = src.shape
@@ -118,16 +119,30 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
               int(angle_base), int(trans_mode), int(bool(use_views)), int(bool(f64_params)), int(k_full), int(k_view),
               float(lr), float(beta1), float(beta2), float(eps), float(loss_scale), _lib.ptr(out_score),
               _lib.ptr(out_loss), _lib.ptr(out_R), _lib.ptr(out_T), _lib.ptr(out_grad), _lib.ptr(out_cd))
+    if large and nn_ws is not None:
+        raise _lib.HouvHipError("solve_iterate: the large-cloud kernel is a brute-force sweep and takes no workspace")
     with torch.cuda.device(src.device):
-        if nn_ws is None:
+        if large:
+            ok = _lib.load().houv_solve_iterate_large(*common, _lib.stream_of(src))
+        elif nn_ws is None:
             ok = _lib.load().houv_solve_iterate(*common, _lib.stream_of(src))
         else:   # exact pruned search: nn_ws int16 [P*K, 16, stride] (solve_workspace) persists between chunked launches
             if nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16) or not nn_ws.is_contiguous():
                 raise _lib.HouvHipError("solve_iterate: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
             ok = _lib.load().houv_solve_iterate_pruned(*common, _lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2],
                                                        _lib.stream_of(src))
-    _lib.check(ok, "houv_solve_iterate" + ("_pruned" if nn_ws is not None else ""))
+    _lib.check(ok, "houv_solve_iterate" + ("_large" if large else "_pruned" if nn_ws is not None else ""))
     return 1
+
+
+def solve_iterate_large_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
+                            k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad=None,
+                            out_cd=None):
+    """``houv_solve_iterate_large`` (clouds of up to 16384 points, none resident in LDS) with solve_iterate_out's arguments:
+    what ``torch.ops.houv.solve_iterate_large`` binds."""
+    return solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
+                             k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd,
+                             large=True)
 
 
 def solve_workspace(n_hypotheses, N, M, device):
@@ -140,8 +155,9 @@ def solve_workspace(n_hypotheses, N, M, device):
 
 def solve_iterate(src, tgt, state, K, *, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                   k_view, lr, loss_scale, betas=(0.9, 0.999), eps=1e-8, want_grad=False, want_cd=False, nn_ws=None,
-                  ws_valid=False):
-    """One launch of the fused HOUV loop (houv_solve_iterate).  ``state`` [P*K,24] fp64 is updated in place.
+                  ws_valid=False, large=False):
+    """One launch of the fused HOUV loop (houv_solve_iterate; ``large``: houv_solve_iterate_large, clouds of up to 16384
+    points).  ``state`` [P*K,24] fp64 is updated in place.
     Returns dict(score[P*K], loss[P*K], R[P*K,3,3], T[P*K,3][, grad[P*K,8]][, cd[P*K,8]]) of the LAST forward."""
     _lib.require_gpu(src, tgt, state)
     dev = src.device
@@ -154,7 +170,7 @@ def solve_iterate(src, tgt, state, K, *, steps_done, n_iters, angle_base, trans_
         out["cd"] = torch.empty((n, 8), dtype=_F32, device=dev)
     solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                       k_view, lr, betas[0], betas[1], eps, loss_scale, out["score"], out["loss"], out["R"], out["T"],
-                      out.get("grad"), out.get("cd"), nn_ws, -1 if ws_valid == "verify" else int(bool(ws_valid)))
+                      out.get("grad"), out.get("cd"), nn_ws, -1 if ws_valid == "verify" else int(bool(ws_valid)), large=large)
     return out
 
 
@@ -231,6 +247,7 @@ def register_torch_ops():
                   "Tensor(e!) out_T, Tensor(f!)? out_grad, Tensor(g!)? out_cd")
     lib.define(f"solve_iterate({solve_args}) -> int")
     lib.define(f"solve_iterate_pruned({solve_args}, Tensor(h!) nn_ws, int ws_valid) -> int")
+    lib.define(f"solve_iterate_large({solve_args}) -> int")
     lib.define("icp_refine(Tensor src, Tensor tgt, Tensor? init, float max_correspondence_distance, int max_iteration, "
                "float relative_fitness, float relative_rmse) -> (Tensor, Tensor, Tensor, Tensor)")
     lib.define("pose_forward(Tensor params, int angle_base, int trans_mode, Tensor? src) -> (Tensor, Tensor, Tensor)")
@@ -240,6 +257,7 @@ def register_torch_ops():
     lib.impl("kabsch", kabsch, "CUDA")
     lib.impl("solve_iterate", solve_iterate_out, "CUDA")
     lib.impl("solve_iterate_pruned", solve_iterate_out, "CUDA")
+    lib.impl("solve_iterate_large", solve_iterate_large_out, "CUDA")
 
     def _icp(src, tgt, init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse):
         r = icp_refine(src, tgt, init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse)

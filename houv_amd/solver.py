@@ -14,7 +14,7 @@ RETRY_THRESHOLD = 0.030      # houv.py:156, train_utils.py:494 (strict >)
 ITERS_PER_LAUNCH = 50        # bound single-launch duration; state round-trips through HBM (192 B/hypothesis)
 
 # bench.py sets this to a list to collect (start_event, end_event, hypotheses, iterations, N, M, use_views, pruned, first) per
-# houv_solve_iterate[_pruned] launch: HIP events recorded on the stream the kernel is launched on.
+# houv_solve_iterate[_pruned|_large] launch: HIP events recorded on the stream the kernel is launched on.
 LAUNCH_LOG = None
 
 # the 26 non-zero {-1,0,1}^3 axes in the reference's loop order (houv.py:44-51)
@@ -218,6 +218,97 @@ def _mark_sorted(cloud, leaf):
 
 FUSED_MAX_POINTS = 4096     # both clouds of a hypothesis live in LDS inside the fused kernel (houv_solve_iterate)
 
+# Clouds of LARGE_MIN_POINTS..LARGE_MAX_POINTS points take houv_solve_iterate_large (csrc/solve_large.hip): the fused loop with
+# neither cloud resident in LDS -- a brute-force sweep, no spatial sort, no workspace.  LARGE_IMPL = "unfused" (HOUV_LARGE=unfused)
+# sends them to _run_stage_unfused instead, for A/B runs; larger clouds always go there.  The routing is on these bounds, not on
+# FUSED_MAX_POINTS.
+LARGE_IMPL = os.environ.get("HOUV_LARGE", "fused").strip().lower()
+LARGE_MIN_POINTS = 4097
+LARGE_MAX_POINTS = 16384
+# One large launch is bounded in duration: at 16384 points a hypothesis-iteration is 2 x 16384^2 point pairs, and 256 pairs x 64
+# restarts of one iteration take ~1.75 s.  run_stage splits the launches along iterations and, when one iteration of every
+# hypothesis is already over the budget, along pairs.  The estimate (large_launch_seconds): one workgroup per CU evaluates
+# LARGE_PAIRS_PER_S_PER_CU point pairs per second, counting the idle lanes of a last, partly filled chunk of 4096 queries; a launch
+# takes ceil(hypotheses / CUs) rounds x iterations of that.  An MI355X measured 18.0-19.6 G pairs/s per CU with the view terms at
+# 4096..16384 points (profiles/r04_perf_large.txt); the constant takes the low end.  0.25 s keeps a launch well under a second
+# with room for a slower clock; a longer one only saves the 192-byte state round trip per hypothesis and launch.
+LARGE_LAUNCH_BUDGET_S = 0.25
+LARGE_PAIRS_PER_S_PER_CU = 18e9
+LARGE_CHUNK = 4096           # queries a houv_solve_iterate_large workgroup sweeps at a time (1024 threads x 4 points)
+
+
+def uses_large(N, M):
+    """Whether run_stage takes houv_solve_iterate_large for clouds of N and M points under the current LARGE_IMPL."""
+    return LARGE_IMPL == "fused" and LARGE_MIN_POINTS <= max(N, M) <= LARGE_MAX_POINTS
+
+
+def large_launch_seconds(hypotheses, iters, N, M, n_cu):
+    """Estimated duration of one houv_solve_iterate_large launch (see LARGE_PAIRS_PER_S_PER_CU)."""
+    pad = lambda x: -(-x // LARGE_CHUNK) * LARGE_CHUNK
+    per_round = (pad(N) * M + pad(M) * N) / LARGE_PAIRS_PER_S_PER_CU     # one hypothesis-iteration on one CU
+    return -(-hypotheses // n_cu) * iters * per_round
+
+
+def large_launch_plan(P, K, N, M, n_cu, budget_s=None):
+    """(pairs, iterations) per houv_solve_iterate_large launch that keep its estimated duration within ``budget_s``
+    (LARGE_LAUNCH_BUDGET_S): as many iterations as fit (at most ITERS_PER_LAUNCH); fewer pairs when a single iteration of all
+    of them would not fit.  At least one pair and one iteration."""
+    budget = LARGE_LAUNCH_BUDGET_S if budget_s is None else budget_s
+    rounds = max(1, int(budget / large_launch_seconds(1, 1, N, M, n_cu)))   # workgroup rounds x iterations a launch may hold
+    pairs = max(1, min(P, rounds * n_cu // K))
+    waves = -(-pairs * K // n_cu)
+    return pairs, max(1, min(ITERS_PER_LAUNCH, rounds // waves))
+
+
+def _run_stage_large(src, tgt, p, K, n_iters, *, angle_base, trans_mode, use_views, f64_params, lr, iters_per_launch,
+                     want_grad, want_cd, alpha, want_last_params):
+    """run_stage for clouds of 4097..16384 points: launches of houv_solve_iterate_large, split along iterations and pairs as
+    large_launch_plan says (bit-neutral: each hypothesis is independent and its state round-trips through HBM exactly)."""
+    from . import _lib
+    _lib.require_gpu(src, tgt)
+    P, N, _ = src.shape
+    M = tgt.shape[1]
+    dev = src.device
+    n = P * K
+    state = torch.zeros((n, 24), dtype=torch.float64, device=dev)
+    state[:, :8] = p.to(dev)
+    k_full, k_view = int(N * alpha), int(N * 1)
+    pairs, step = large_launch_plan(P, K, N, M, torch.cuda.get_device_properties(dev).multi_processor_count)
+    if iters_per_launch:
+        step = min(step, iters_per_launch)
+    last_params = torch.empty((n, 8), dtype=torch.float64, device=dev) if want_last_params else None
+    outs = []
+    for p0 in range(0, P, pairs):
+        p1 = min(P, p0 + pairs)
+        rows = slice(p0 * K, p1 * K)
+        s_src, s_tgt, s_state = src[p0:p1], tgt[p0:p1], state[rows]
+        done, out = 0, None
+        while done < n_iters:
+            it = min(step, n_iters - done)
+            if want_last_params:
+                if done == n_iters - 1:
+                    last_params[rows] = s_state[:, :8]
+                else:
+                    it = min(it, n_iters - 1 - done)
+            last = done + it == n_iters
+            if LAUNCH_LOG is not None:
+                ev0 = torch.cuda.Event(enable_timing=True)
+                ev1 = torch.cuda.Event(enable_timing=True)
+                ev0.record(torch.cuda.current_stream(dev))
+            out = ops.solve_iterate(s_src, s_tgt, s_state, K, steps_done=done, n_iters=it, angle_base=angle_base,
+                                    trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
+                                    k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad and last,
+                                    want_cd=want_cd and last, large=True)
+            if LAUNCH_LOG is not None:
+                ev1.record(torch.cuda.current_stream(dev))
+                LAUNCH_LOG.append((ev0, ev1, (p1 - p0) * K, it, N, M, bool(use_views), False, done == 0))
+            done += it
+        outs.append(out)
+    out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
+    if want_last_params:
+        out["last_params"] = last_params
+    return out, state
+
 
 def _run_stage_unfused(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views, f64_params, lr, want_grad,
                        want_cd, alpha):
@@ -296,6 +387,10 @@ def run_stage(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views
     p = torch.as_tensor(params, dtype=torch.float64)
     if tuple(p.shape) != (n, 8):
         raise ValueError(f"params must be [{n},8]")
+    if uses_large(N, tgt.shape[1]):
+        return _run_stage_large(src, tgt, p, K, n_iters, angle_base=angle_base, trans_mode=trans_mode, use_views=use_views,
+                                f64_params=f64_params, lr=lr, iters_per_launch=iters_per_launch, want_grad=want_grad,
+                                want_cd=want_cd, alpha=alpha, want_last_params=want_last_params)
     if max(N, tgt.shape[1]) > FUSED_MAX_POINTS:
         from . import _lib
         _lib.require_gpu(src, tgt)

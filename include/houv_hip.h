@@ -125,6 +125,25 @@ int houv_solve_iterate_pruned(const float* src, const float* tgt, int P, int N, 
                               float* out_grad, float* out_cd,
                               int16_t* nn_ws, int ws_valid, int ws_stride, void* stream);
 
+/* Fused loop for LARGE clouds (what houv_amd.solver runs for 4097..16384 points): the same arguments, outputs and arithmetic
+ * contract as houv_solve_iterate, for clouds that do not fit in LDS.  Neither cloud is resident: every workgroup (1024 threads,
+ * one hypothesis) holds 4096 query points at a time in registers and streams the other cloud through a double-buffered LDS
+ * tile (2 x 1024 points x 16 B); per query only the full metric's minimum and nearest-neighbour unit are kept (6 B of LDS) for
+ * its top-k.  LDS per workgroup: 40048 + 6 * max(N, M) bytes (135 KiB at 16384 points); no scratch; one workgroup per CU.
+ * Brute force: 2 N M point pairs per hypothesis-iteration -- bound the work per call (houv_amd.solver splits calls along
+ * iterations and pairs).  Same search result as houv_solve_iterate; the sums are grouped differently, so outputs agree to
+ * fp32 rounding, not bit for bit.  Deterministic, and chunking along iterations (steps_done) is bit-neutral.
+ * Limits: 1 <= N, M <= HOUV_LARGE_MAX_POINTS; with use_views, N == M and k_view == N (the reference's loss_view raises
+ * otherwise); 1 <= k_full <= min(N, M).  Returns 0 with houv_last_error() set, launching nothing, when a check fails. */
+#define HOUV_LARGE_MAX_POINTS 16384
+int houv_solve_iterate_large(const float* src, const float* tgt, int P, int N, int M, int K,
+                             double* state, int steps_done, int n_iters,
+                             int angle_base, int trans_mode, int use_views, int f64_params,
+                             int k_full, int k_view,
+                             double lr, double beta1, double beta2, double eps, float loss_scale,
+                             float* out_score, float* out_loss, float* out_R, float* out_T,
+                             float* out_grad, float* out_cd, void* stream);
+
 /* Which kernel variant the two entry points above launch for clouds of N and M points (host-only query, no GPU work):
  * *block = threads per workgroup (256 / 512 / 1024), *points_per_lane = query points a lane owns (1..4), *prune_mode =
  * 0 brute-force sweep, 1 pruned search walked by the owning lanes, 2 / 3 pruned search with the balanced (sorted-block) walk over
