@@ -11,22 +11,28 @@ solves its own batch of the same size (weak scaling; pairs are independent, no d
 exchange the per-pair (R,t) of all timed steps with ONE RCCL all-gather inside the timed region.  Rank 0 prints one JSON line.
 
 `value` = the DEFAULT product path: the exact pruned nearest-neighbour search (houv_solve_iterate_pruned; --solver brute times the
-brute-force sweep instead).  Extra objects on the line:
+brute-force sweep instead).  A plain run does only what that figure needs: it makes the batches, warms up, times the steps, writes
+--dump-outputs and prints the line with `config`, `quality` and (N > 1) `ranks`.  --full adds what takes runs of its own:
   roofline      the dominant kernel of the timed run (houv::solve_kernel<512, 4, 4, 2, 1>), timed live with HIP events on its launch
                 stream; `frac` = EXECUTED fp32 flops of the nearest-neighbour evaluations / 157.3 TFLOP/s (see `frac_definition`);
                 `pruned_search` = what the search visited; `sustained_clock_ghz` = measured inside the kernel; `traffic` and the
                 `valu_*` figures = the committed PMC pass, printed only when it profiled the loaded library build
   brute_force   EVERY timed batch again through the brute-force sweep (houv_solve_iterate): pairs/s, whether every transform came out
                 bit-identical to the timed run, and that kernel's own roofline (+ the VALU issue-slot model)
-  ranks         N > 1 (or --force-process-group): per-rank seconds, retried pairs, gather time, load balance
   chamfer_op    the stand-alone Chamfer op at the same cloud size (BASELINE metric's "Chamfer HBM GB/s" half)
   cpu_baseline  the CPU oracle (oracle/houv_ref_cpu.py, the reference's PyTorch-CPU formulation) on a bounded sample
+(brute_force, chamfer_op and cpu_baseline at N = 1 only; --no-other-solver / --no-chamfer-op / --no-cpu-baseline drop one of them).
+With --dcp, --full adds the `roofline` of the GEMM and attention kernels, timed in one extra eager step.
+Always on the line:
+  ranks         N > 1 (or --force-process-group): per-rank seconds, retried pairs, gather time, load balance
 """
 import argparse
 import json
+import multiprocessing as mp
 import os
 import sys
 import time
+from concurrent.futures import ProcessPoolExecutor
 
 import numpy as np
 import torch
@@ -69,6 +75,10 @@ def parse():
     ap.add_argument("--solver", default="pruned", choices=["brute", "pruned"],
                     help="pruned = the product default: exact pruned search, bit-identical to the brute-force sweep on the same "
                          "clouds; brute = the brute-force sweep north_star specifies (then the other leg is `pruned`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need and what takes runs of its own: the timed kernel's "
+                         "roofline (one extra counters stage), the other search's leg, the Chamfer op and the CPU oracle "
+                         "baseline (with --dcp: the kernels' roofline from one extra eager step)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-solver", action="store_true",
                     help="skip the leg that re-runs every timed batch through the other search (bit-identity + its roofline)")
@@ -85,6 +95,38 @@ def parse():
 
 
 DUMP_LIMIT_BYTES = 64 << 20
+HOST_CPUS = 16                 # host cores a one-GPU job is granted (oversubscribing all visible cores is slower)
+PARALLEL_MIN_PAIRS = 512       # below this many pairs (~3 s) the synthetic batches are made in this process
+PAIRS_PER_JOB = 16
+
+
+def _pair_run(job):
+    """Worker: synthetic.make_pair for `n` consecutive pair ids, stacked as make_pairs stacks them."""
+    from houv_amd import synthetic
+    first, n, points, seed = job
+    out = [synthetic.make_pair(first + i, points, seed) for i in range(n)]
+    return tuple(np.stack([o[k] for o in out]) for k in range(3))
+
+
+def host_batches(pairs, points, first_ids, seed=2021, min_pairs=PARALLEL_MIN_PAIRS):
+    """[synthetic.make_pairs(pairs, points, seed, first_id) for first_id in first_ids], bit for bit.  Every pair has its own
+    seed (seed + pair id), so large runs make their pairs in worker processes.  The workers come from a fork server, which
+    must be started before this process opens the GPU: main() calls this first, and once torch has initialised the GPU the
+    pairs are made in-process."""
+    from houv_amd import synthetic
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
+    workers = min(len(os.sched_getaffinity(0)), HOST_CPUS) // max(local_world, 1)
+    if workers < 2 or pairs * len(first_ids) < min_pairs or torch.cuda.is_initialized():
+        return [synthetic.make_pairs(pairs, points, seed=seed, first_id=f) for f in first_ids]
+    jobs = [(f + i, min(PAIRS_PER_JOB, pairs - i), points, seed) for f in first_ids for i in range(0, pairs, PAIRS_PER_JOB)]
+    with ProcessPoolExecutor(workers, mp_context=mp.get_context("forkserver")) as ex:
+        runs = list(ex.map(_pair_run, jobs))
+    per_batch = len(runs) // len(first_ids)
+    out = []
+    for b in range(len(first_ids)):
+        part = runs[b * per_batch:(b + 1) * per_batch]
+        out.append(tuple(torch.from_numpy(np.concatenate([r[k] for r in part])) for k in range(3)))
+    return out
 
 
 def dump_outputs(out_dir, arrays):
@@ -324,20 +366,17 @@ def chamfer_op_probe(dev, points):
                     "metric asks for it (a brute-force 2048^2 sweep cannot exceed ~2.4 % of HBM peak)"}
 
 
-def bench_dcp(args, dev, world, rank):
+def bench_dcp(args, dev, world, rank, host):
     """configs[4]: one step = DCP forward (DGCNN + Transformer pointer + SVD head) over the batch, then the HOUV robust
     Chamfer loss (Predict_loss, houv.py:209-222) of the source cloud moved by DCP's answer.  Weights are random-init
     (the reference ships no checkpoint), so only throughput and the loss plumbing are meaningful, not accuracy."""
-    from houv_amd import ops, synthetic
+    from houv_amd import ops
     from houv_amd.models.dcp import Model
     from houv_amd.models.houv import Predict_loss
     P = args.pairs
     torch.manual_seed(2021)
     net = Model(None, pairs_per_chunk=int(os.environ.get("HOUV_DCP_CHUNK", 32))).to(dev)
-    batches = []
-    for b in range(args.steps + args.warmup):
-        s, t, _ = synthetic.make_pairs(P, args.points, seed=2021, first_id=(b * world + rank) * P)
-        batches.append((s.to(dev), t.to(dev)))
+    batches = [(s.to(dev), t.to(dev)) for s, t, _ in host]
     losses = []
     last = {}
 
@@ -365,20 +404,19 @@ def bench_dcp(args, dev, world, rank):
     dt = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, last)          # before the extra step below runs the last batch again
-    # kernel times for `roofline`: ONE more step, outside the timed region, launched eagerly with an event pair around every
-    # houv_gemm_f32 / houv_attention_f32 call (events cannot be recorded inside a graph replay)
-    n_timed = len(losses)
-    ops.GEMM_LOG = []
-    step(args.warmup + args.steps - 1)
-    sync()
-    log, ops.GEMM_LOG = ops.GEMM_LOG, None
-    del losses[n_timed:]
+    if args.full:
+        # kernel times for `roofline`: ONE more step, outside the timed region, launched eagerly with an event pair around every
+        # houv_gemm_f32 / houv_attention_f32 call (events cannot be recorded inside a graph replay)
+        n_timed = len(losses)
+        ops.GEMM_LOG = []
+        step(args.warmup + args.steps - 1)
+        sync()
+        log, ops.GEMM_LOG = ops.GEMM_LOG, None
+        del losses[n_timed:]
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    g_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in log)
-    g_fl = sum(f for _, _, f in log)
     out = {
         "metric": "registration pairs/sec (2048-pt partial pairs)", "value": P * world * args.steps / dt,
         "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -388,22 +426,26 @@ def bench_dcp(args, dev, world, rank):
                                f"batch {P}/GPU (BASELINE configs[4])", "pairs_per_gpu": P, "points": args.points,
                    "parallelism": f"dp{world}"},
         "quality": {"mean_houv_loss_of_dcp_answer": float(np.mean(losses[-args.steps:]))},
+    }
+    if args.full:
+        g_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in log)
+        g_fl = sum(f for _, _, f in log)
         # the GEMMs and the attention run on the bf16 matrix pipe with every fp32 product summed from SIX bf16 part products
         # (houv_split.h): the pipe executes 6 bf16 flops per useful fp32 flop, so `achieved` / `frac` price the executed work against
         # the dense bf16 peak and `useful_fp32_tflops` says what the model got out of it (the fp32-input MFMA peak is 157.3)
-        "roofline": {"kernel": "houv::gemm_split_kernel<.., 6> + houv::attention_split_kernel (v_mfma_f32_32x32x16_bf16, six bf16 "
-                               "part products per fp32 product)", "bound": "mfma",
-                     "achieved": 6.0 * g_fl / (g_ms * 1e-3) / 1e12, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": 6.0 * g_fl / (g_ms * 1e-3) / 1e12 / BF16_PEAK_TFLOPS,
-                     "useful_fp32_tflops": g_fl / (g_ms * 1e-3) / 1e12,
-                     "useful_over_fp32_input_mfma_peak": g_fl / (g_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
-                     "note": "HIP-event time of every houv_gemm_f32 / houv_attention_f32 call of one step (the attention's split pre-pass included); "
-                             "the short-K 1x1 convolutions of the DGCNN are HBM-bound inside it (DESIGN.md 9.2)",
-                     "traffic": None, "launches": len(log),
-                     "avg_launch_ms": g_ms / max(len(log), 1), "kernel_time_share": g_ms * 1e-3 / (dt / args.steps),
-                     "kernel_times_from": "one extra eager step outside the timed region (the timed steps replay HIP graphs)",
-                     "hip_graphs": bool(net.use_graphs and net._graphs)},
-    }
+        out["roofline"] = {
+            "kernel": "houv::gemm_split_kernel<.., 6> + houv::attention_split_kernel (v_mfma_f32_32x32x16_bf16, six bf16 "
+                      "part products per fp32 product)", "bound": "mfma",
+            "achieved": 6.0 * g_fl / (g_ms * 1e-3) / 1e12, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": 6.0 * g_fl / (g_ms * 1e-3) / 1e12 / BF16_PEAK_TFLOPS,
+            "useful_fp32_tflops": g_fl / (g_ms * 1e-3) / 1e12,
+            "useful_over_fp32_input_mfma_peak": g_fl / (g_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
+            "note": "HIP-event time of every houv_gemm_f32 / houv_attention_f32 call of one step (the attention's split pre-pass "
+                    "included); the short-K 1x1 convolutions of the DGCNN are HBM-bound inside it (DESIGN.md 9.2)",
+            "traffic": None, "launches": len(log),
+            "avg_launch_ms": g_ms / max(len(log), 1), "kernel_time_share": g_ms * 1e-3 / (dt / args.steps),
+            "kernel_times_from": "one extra eager step outside the timed region (the timed steps replay HIP graphs)",
+            "hip_graphs": bool(net.use_graphs and net._graphs)}
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -416,6 +458,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    # synthetic MVP-shaped pairs, a different slice per rank and per step, made before this process opens the GPU
+    n_batches = args.steps + args.warmup
+    host = host_batches(args.pairs, args.points, [(b * world + rank) * args.pairs for b in range(n_batches)])
     assert torch.cuda.is_available(), "bench.py needs MI355X GPUs (there is no CPU fallback)"
     if args.single_device:
         local = 0
@@ -431,20 +476,18 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
     from houv_amd import distributed as hd
-    from houv_amd import solver, synthetic
+    from houv_amd import solver
     from houv_amd.models.houv import HOUV
 
     if args.dcp:
-        return bench_dcp(args, dev, world, rank)
+        return bench_dcp(args, dev, world, rank, host)
     P = args.pairs
     n_total = P * world
     solver.PRUNED = args.solver == "pruned"          # the product default (houv_amd.solver.PRUNED) unless --solver brute
     use_pruned = solver.uses_pruned(args.points, args.points)
-    # synthetic MVP-shaped pairs, a different slice per rank and per step; resident in HBM before timing starts
-    n_batches = args.steps + args.warmup
+    # the batches are resident in HBM before timing starts
     batches = []
-    for b in range(n_batches):
-        s, t, pose = synthetic.make_pairs(P, args.points, seed=2021, first_id=(b * world + rank) * P)
+    for s, t, pose in host:
         # The order of the points of a cloud carries no meaning.  The pruned search sorts both clouds into k-d leaves of 32 points
         # (solver.run_stage does it; sorting a sorted cloud is the identity); sorting them here, once, outside the timed
         # region makes the brute-force leg see IDENTICAL inputs, so that the two searches can be compared bit for bit
@@ -556,14 +599,13 @@ def main():
     all_inst_iters = sum(n * it for _, _, n, it, *_ in log)
     log_base = [e for e in log if e[2] == P * args.kernel]
     stats = None
-    if rank == 0:
+    if args.full and rank == 0:
         solver.LAUNCH_LOG = []
         stats = solve_stats_pass(lambda s, t: solver.run_stage(
             s, t, solver.houv_init_params(P * args.kernel), args.kernel, min(args.iters, 50), angle_base=0, trans_mode=0,
             use_views=True, f64_params=False, lr=0.01), batches[b_last])
         log_all = log_all + solver.LAUNCH_LOG          # the profiler sees this launch too (launches_incl_warmup)
         solver.LAUNCH_LOG = None
-    roofline = kernel_roofline(log_base, log_all, dt, all_inst_iters, len(log) - len(log_base), stats, args.points)
     out = {
         "metric": "registration pairs/sec (2048-pt partial pairs)", "value": n_total * args.steps / dt,
         "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -575,7 +617,7 @@ def main():
                    "pairs_per_gpu": P, "points": args.points, "kernel": args.kernel, "iters": args.iters,
                    "icp_refine": bool(args.icp),
                    "solver": ("pruned: exact pruned nearest-neighbour search, the product default -- bit-identical to the "
-                              "brute-force sweep on the same clouds (see `brute_force`)") if use_pruned else
+                              "brute-force sweep on the same clouds (see `brute_force` of a --full run)") if use_pruned else
                              "brute: the brute-force sweep of north_star's formulation",
                    "parallelism": f"dp{world} (pair shards, one {'RCCL' if args.backend == 'nccl' else 'gloo'} "
                                   "all-gather of [steps*P,12] per rank)"},
@@ -584,11 +626,12 @@ def main():
                     "hypothesis_iterations_per_pair": all_inst_iters / (P * args.steps),
                     "note": "synthetic pairs, 20 % of them with up to 180 deg of relative rotation: not comparable with the "
                             "reference's MVP leaderboard figures"},
-        "roofline": roofline,
     }
+    if args.full:
+        out["roofline"] = kernel_roofline(log_base, log_all, dt, all_inst_iters, len(log) - len(log_base), stats, args.points)
     if per_rank is not None:
         out["ranks"] = per_rank
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_other_solver and not args.icp:
             timed = [b for b, _ in results]
             leg = other_solver_leg(args, dev, batches, timed, {b: a for b, a in results}, make_solve, P)

@@ -18,7 +18,7 @@ run sq2 SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_
 run grbm GRBM_GUI_ACTIVE GRBM_COUNT
 run fetch FETCH_SIZE
 run write WRITE_SIZE
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || echo "trace failed"
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || echo "trace failed"
 python3 scripts/pmc_summary.py $OUT > $OUT/pmc_summary.txt 2>&1 || true
 python3 scripts/pmc_calib_summary.py $OUT > $OUT/pmc_calib_summary.txt 2>&1 || true
 find $OUT -name "*kernel_stats.csv" | head -3

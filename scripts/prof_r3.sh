@@ -18,6 +18,6 @@ run write WRITE_SIZE
 python3 scripts/pmc_summary_r3.py $OUT > $OUT/pmc_summary.txt 2>&1 || true
 cat $OUT/pmc_summary.txt | grep -E "INSTS_VALU |GRBM_GUI|FETCH|WRITE|BUSY_CYC|us per" | head -40
 if [ "$1" = "trace" ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || echo "trace failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || echo "trace failed"
   find $OUT/trace -name "*kernel_stats.csv" | head -3
 fi

@@ -1,5 +1,6 @@
 """The driver's bench contract, exercised on a miniature workload in-process (bench.py is a script: argv in, ONE JSON line
-out): field names / types, the roofline and brute_force / pruned objects, and internal consistency of the numbers."""
+out): field names / types, the roofline and brute_force / pruned objects of a --full run, what a plain run leaves out, and
+internal consistency of the numbers."""
 import io
 import json
 import os
@@ -31,7 +32,7 @@ def _run(argv, monkeypatch):
 
 def test_bench_line_contract(monkeypatch, tmp_path):
     d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "8", "--points", "768", "--kernel", "26",
-              "--iters", "40", "--no-cpu-baseline", "--no-chamfer-op", "--dump-outputs", str(tmp_path)], monkeypatch)
+              "--iters", "40", "--full", "--no-cpu-baseline", "--no-chamfer-op", "--dump-outputs", str(tmp_path)], monkeypatch)
     # --dump-outputs: solve_model's (r_err, t_err, ans) of the last timed step, the arrays the quality figures come from
     import numpy as np
     ans, r_err, t_err = (np.load(tmp_path / f"{n}.npy") for n in ("ans", "rot_err_deg", "trans_err"))
@@ -77,13 +78,31 @@ def test_bench_line_contract(monkeypatch, tmp_path):
 def test_bench_brute_solver_flag(monkeypatch):
     """--solver brute times north_star's brute-force formulation; the other leg is then the pruned search."""
     d = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--pairs", "8", "--points", "768", "--kernel", "26",
-              "--iters", "30", "--no-cpu-baseline", "--no-chamfer-op", "--solver", "brute"], monkeypatch)
+              "--iters", "30", "--full", "--no-cpu-baseline", "--no-chamfer-op", "--solver", "brute"], monkeypatch)
     assert "solve_kernel<256, 3, 4, 0, 1>" in d["roofline"]["kernel"] and d["config"]["solver"].startswith("brute")
     assert d["pruned"]["bit_identical_to_timed_run"] is True and "4, 2, 1>" in d["pruned"]["roofline"]["kernel"]
     # up to 256 points both searches are the brute-force kernel: nothing to compare, and the line says so
     d = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--pairs", "8", "--points", "256", "--kernel", "26",
-              "--iters", "20", "--no-cpu-baseline", "--no-chamfer-op"], monkeypatch)
+              "--iters", "20", "--full", "--no-cpu-baseline", "--no-chamfer-op"], monkeypatch)
     assert "solve_kernel<256, 1, 4, 0, 1>" in d["roofline"]["kernel"] and "skipped" in d["brute_force"]
+
+
+def test_bench_plain_run_is_lean(monkeypatch, tmp_path):
+    """Without --full the line has the headline, `config` and `quality` and nothing that takes a run of its own (the CPU
+    baseline and the Chamfer op are not switched off here: a plain run must skip them by itself).  --full times the same
+    steps: its dumped outputs equal the plain run's."""
+    import numpy as np
+    argv = ["--gpus", "1", "--steps", "1", "--warmup", "1", "--pairs", "8", "--points", "768", "--kernel", "26", "--iters", "30"]
+    d = _run(argv + ["--dump-outputs", str(tmp_path / "plain")], monkeypatch)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "quality"):
+        assert key in d, key
+    assert d["steps"] == 1 and d["warmup"] == 1 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "brute_force", "pruned", "chamfer_op", "cpu_baseline", "ranks"} & set(d), sorted(d)
+    f = _run(argv + ["--full", "--no-cpu-baseline", "--no-chamfer-op", "--no-other-solver", "--dump-outputs",
+                     str(tmp_path / "full")], monkeypatch)
+    assert "roofline" in f and f["quality"]["hypothesis_iterations_per_pair"] == d["quality"]["hypothesis_iterations_per_pair"]
+    for name in ("ans", "rot_err_deg", "trans_err"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")), name
 
 
 def test_bench_one_rank_through_rccl():
