@@ -9,7 +9,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# HOUV_HIP_LIB lets the diagnostic scripts load the stamped build variant; the default is the product library
+# HOUV_HIP_LIB lets the A/B scripts load another build of the library; the default is the product library
 LIB_PATH = os.environ.get("HOUV_HIP_LIB") or os.path.join(_HERE, "lib", "libhouv_hip.so")
 ABI_VERSION = 2
 

@@ -61,19 +61,16 @@ extern "C" const char* houv_last_error(void) { return houv::g_err; }
 
 extern "C" int houv_debug_set(const char* name, long long value) {
   using namespace houv;
-  const struct { const char* name; std::atomic<int>* knob; long long lo, hi; } ints[] = {
-      {"solve_predict", &g_debug.pred_mode, 0, 2},   {"prune_refresh", &g_debug.ws_refresh, 0, 1 << 30},
-      {"prune_cap_slack", &g_debug.prune_cap_slack, -1, 64}, {"prune_owner_walk", &g_debug.prune_owner_walk, 0, 1}, {"prune_min_points", &g_debug.prune_min_points, 257, 2049},
-      {"chamfer_direct", &g_debug.chamfer_direct, 0, 1}, {"chamfer_q", &g_debug.chamfer_q, 1, 8},
-      {"gemm_4w", &g_debug.gemm_4w, 0, 1},           {"gemm_guarded", &g_debug.gemm_guarded, 0, 1},
-      {"gemm_split", &g_debug.gemm_split, 0, 6},     {"attn_split", &g_debug.attn_split, 0, 1},
-      {"knn_split", &g_debug.knn_split, 0, 1}};
+  // accepted values: lo..hi in steps of `step` (gemm_split: 0, 3 or 6 part products -- any other count is not a kernel)
+  const struct { const char* name; std::atomic<int>* knob; long long lo, hi, step; } ints[] = {
+      {"solve_predict", &g_debug.pred_mode, 0, 2, 1}, {"knn_split", &g_debug.knn_split, 0, 1, 1},
+      {"attn_split", &g_debug.attn_split, 0, 1, 1},   {"gemm_split", &g_debug.gemm_split, 0, 6, 3}};
   if (name && !strcmp(name, "solve_stats")) {
     g_debug.stats = (unsigned long long)value;
     return 1;
   }
   for (const auto& k : ints)
-    if (name && !strcmp(name, k.name) && value >= k.lo && value <= k.hi) {
+    if (name && !strcmp(name, k.name) && value >= k.lo && value <= k.hi && value % k.step == 0) {
       *k.knob = (int)value;
       return 1;
     }

@@ -7,9 +7,9 @@
 //   * every lane owns Q query points in registers, the reference cloud is staged through LDS as
 //     float4 and read back with wave-uniform (broadcast) ds_read_b128, so one LDS read feeds
 //     64 x Q distance evaluations;
-//   * the inner loop is min-only (v_min3_f32 over two references at a time); the arg-min is
-//     tracked per 32-reference sub-tile and recovered exactly afterwards by re-evaluating that one
-//     sub-tile with bit-identical arithmetic ("deferred index");
+//   * the inner loop is min-only (v_min3_f32 over two references at a time) on an expanded-form filter
+//     value; the arg-min is tracked per 32-reference sub-tile and recovered exactly afterwards by
+//     re-evaluating the candidate sub-tiles with the reference's direct-difference arithmetic;
 //   * the running minimum lives in registers for the whole sweep (the reference spills it to global
 //     memory every 512 references, chamfer3D.cu:126-129).
 #include <stdlib.h>
@@ -22,105 +22,12 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kRefTile = 2048;   // references staged per LDS pass: 2048 * 16 B = 32 KiB
 
-template <int Q>
-__global__ __launch_bounds__(kBlock) void chamfer_nn_kernel(const float* __restrict__ xyz1,
-                                                            const float* __restrict__ xyz2, int N, int M, int nqb,
-                                                            float* __restrict__ dist1, float* __restrict__ dist2,
-                                                            int* __restrict__ idx1, int* __restrict__ idx2) {
-  __shared__ float4 s_ref[kRefTile];
-  const bool fwd = blockIdx.y == 0;
-  const int nq = fwd ? N : M, nr = fwd ? M : N;
-  const int b = blockIdx.x / nqb;
-  const int q0 = (blockIdx.x - b * nqb) * (kBlock * Q);
-  if (q0 >= nq) return;   // uniform for the whole workgroup (grid is sized for max(N, M))
-  const float* __restrict__ q = (fwd ? xyz1 : xyz2) + (size_t)b * nq * 3;
-  const float* __restrict__ r = (fwd ? xyz2 : xyz1) + (size_t)b * nr * 3;
-  float* __restrict__ dist = (fwd ? dist1 : dist2) + (size_t)b * nq;
-  int* __restrict__ idx = (fwd ? idx1 : idx2) + (size_t)b * nq;
-  const int tid = threadIdx.x;
-
-  float qx[Q], qy[Q], qz[Q], best[Q];
-  int btile[Q];
-#pragma unroll
-  for (int k = 0; k < Q; ++k) {
-    const int qi = q0 + k * kBlock + tid;
-    const bool ok = qi < nq;
-    qx[k] = ok ? q[qi * 3 + 0] : 0.f;
-    qy[k] = ok ? q[qi * 3 + 1] : 0.f;
-    qz[k] = ok ? q[qi * 3 + 2] : 0.f;
-    best[k] = INFINITY;
-    btile[k] = 0;
-  }
-
-  for (int r0 = 0; r0 < nr; r0 += kRefTile) {
-    const int cnt = min(kRefTile, nr - r0);
-    const int ntile = (cnt + kSub - 1) / kSub;
-    __syncthreads();
-    for (int j = tid; j < ntile * kSub; j += kBlock) {
-      float4 v = make_float4(INFINITY, INFINITY, INFINITY, 0.f);   // padding never wins
-      if (j < cnt) {
-        const float* p = r + (size_t)(r0 + j) * 3;
-        v = make_float4(p[0], p[1], p[2], 0.f);
-      }
-      s_ref[j] = v;
-    }
-    __syncthreads();
-    for (int t = 0; t < ntile; ++t) {
-      float tm[Q];
-#pragma unroll
-      for (int k = 0; k < Q; ++k) tm[k] = INFINITY;
-      const float4* rp = s_ref + t * kSub;
-#pragma unroll 8
-      for (int j = 0; j < kSub; j += 2) {
-        const float4 a = rp[j], c = rp[j + 1];
-        asm volatile("" ::"v"(a.w), "v"(c.w));   // keep the loads ds_read_b128 (4 LDS cycles, not b96's 8)
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-          const float d0 = metric_sqdist<0>(a.x - qx[k], a.y - qy[k], a.z - qz[k]);
-          const float d1 = metric_sqdist<0>(c.x - qx[k], c.y - qy[k], c.z - qz[k]);
-          tm[k] = min3f(tm[k], d0, d1);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < Q; ++k) {
-        const bool lt = tm[k] < best[k];   // strict: the earlier sub-tile keeps ties
-        best[k] = lt ? tm[k] : best[k];
-        btile[k] = lt ? (r0 / kSub + t) : btile[k];
-      }
-    }
-  }
-
-  // exact index recovery: re-evaluate the winning sub-tile (descending, so the lowest index wins)
-#pragma unroll
-  for (int k = 0; k < Q; ++k) {
-    const int qi = q0 + k * kBlock + tid;
-    if (qi >= nq) continue;
-    const int base = btile[k] * kSub;
-    int found = base;
-    float bd = best[k];
-    if (!(bd < INFINITY)) {
-      // no finite distance at all (NaN / overflowing input): the reference reports ref 0 (chamfer3D.cu:37)
-      bd = metric_sqdist<0>(r[0] - qx[k], r[1] - qy[k], r[2] - qz[k]);
-      found = 0;
-    } else {
-      for (int j = kSub - 1; j >= 0; --j) {
-        const int jj = base + j;
-        if (jj < nr) {
-          const float d = metric_sqdist<0>(r[jj * 3 + 0] - qx[k], r[jj * 3 + 1] - qy[k], r[jj * 3 + 2] - qz[k]);
-          found = (d == bd) ? jj : found;
-        }
-      }
-    }
-    dist[qi] = bd;
-    idx[qi] = found;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// Filtered sweep (the default): the SAME result as chamfer_nn_kernel, bit for bit, for 4.4 instead of 7.1 VALU issue
-// slots per point pair.
+// Filtered sweep: per query the minimum over the references of d = fma(dz,dz,fma(dy,dy,dx*dx)) with (dx,dy,dz) = reference -
+// query (metric_sqdist<0>: nvcc's contraction of chamfer3D.cu:31-36) and the LOWEST index attaining it -- bit for bit the
+// C oracle (oracle/chamfer_ref.c) -- for 4.4 VALU issue slots per point pair instead of a direct-difference sweep's 7.1.
 //   * filter: e_j = |r_j|^2 - 2 q.r_j  (= |q - r_j|^2 - |q|^2) as three FMAs on (x, y, z, |r|^2) float4 references --
-//     the .w slot of the LDS tile, unused by the direct sweep, carries |r|^2, so the LDS traffic is unchanged;
+//     |r|^2 rides in the .w slot of the LDS tile, so the LDS traffic is that of a direct-difference sweep;
 //   * e differs from the exact direct-difference d (the reference's arithmetic, chamfer3D.cu:31-36) by rounding, so
 //     it only SELECTS: per query the two smallest sub-tile minima of e (and their sub-tiles) plus the third smallest
 //     value are tracked (v_med3 updates, 8 instructions per query and 32 references); afterwards
@@ -131,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void chamfer_nn_kernel(const float* __restr
 //       |e~ - E| <= 6.02 u (R + |q|)^2   (3 roundings for |r|^2, 3 for the FMA chain),   |d - D| <= 5.01 u D,
 //     so the oracle's arg-min j* satisfies  e~(j*) <= e~(j) + 2 * 6.02 u (R+|q|)^2 + 10.1 u D_j  for every j;
 //     tau = 25 u (R + |q|)^2 covers it (derivation in DESIGN.md 3.2).  NaN / Inf coordinates behave as in the
-//     direct kernel: such references never win (v_min3 drops NaN), and a query without any finite distance reports
+//     reference: such references never win (v_min3 drops NaN), and a query without any finite distance reports
 //     reference 0 (chamfer3D.cu:37).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr float kUlpHalf = 5.9604645e-8f;   // u = 2^-24
@@ -290,12 +197,10 @@ __global__ __launch_bounds__(kBlock, 4) void chamfer_nn_filter_kernel(const floa
     for (int o = 32; o > 0; o >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, o, kWave));
     if ((tid & 63) == 0) atomicMax(&s_rmax, __float_as_uint(lmax));
     __syncthreads();
-#ifndef HOUV_CHAMFER_COMPILED_SWEEP
     if constexpr (Q == 8) {
       filter_sweep8((unsigned)(size_t)(const __attribute__((address_space(3))) float4*)s_ref, ntile, r0 / kSub, ex, ey, ez, best, sec, third, bt, bt2);
       continue;
     }
-#endif
     for (int t = 0; t < ntile; ++t) {
       float tm[Q];
 #pragma unroll
@@ -618,27 +523,17 @@ extern "C" int houv_chamfer_forward(const float* xyz1, const float* xyz2, int B,
   }
   hipStream_t s = (hipStream_t)stream;
   const int mx = N > M ? N : M;
-  const bool direct = g_debug.chamfer_direct.load() != 0;   // houv_debug_set: A/B diagnostics only
-  const int qmax = g_debug.chamfer_q.load();
-  int q = mx <= kBlock ? 1 : (mx <= 2 * kBlock ? 2 : (mx <= 4 * kBlock || direct ? 4 : 8));
-  if (q > qmax) q = qmax;
+  const int q = mx <= kBlock ? 1 : (mx <= 2 * kBlock ? 2 : (mx <= 4 * kBlock ? 4 : 8));
   const int nqb = (mx + kBlock * q - 1) / (kBlock * q);
   if ((long long)B * nqb > 0x7fffffffLL) {
     set_error("houv_chamfer_forward: batch too large");
     return 0;
   }
   dim3 grid((unsigned)(B * nqb), 2, 1);
-  // HOUV_CHAMFER_DIRECT=1 (diagnostics / A-B only): the direct-difference sweep without the expanded-form filter
-  if (direct) {
-    if (q == 1) chamfer_nn_kernel<1><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-    else if (q == 2) chamfer_nn_kernel<2><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-    else chamfer_nn_kernel<4><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-  } else {
-    if (q == 1) chamfer_nn_filter_kernel<1><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-    else if (q == 2) chamfer_nn_filter_kernel<2><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-    else if (q == 4) chamfer_nn_filter_kernel<4><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-    else chamfer_nn_filter_kernel<8><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
-  }
+  if (q == 1) chamfer_nn_filter_kernel<1><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
+  else if (q == 2) chamfer_nn_filter_kernel<2><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
+  else if (q == 4) chamfer_nn_filter_kernel<4><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
+  else chamfer_nn_filter_kernel<8><<<grid, kBlock, 0, s>>>(xyz1, xyz2, N, M, nqb, dist1, dist2, idx1, idx2);
   return check_launch("houv_chamfer_forward") ? 1 : 0;
 }
 

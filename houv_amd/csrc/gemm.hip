@@ -11,8 +11,7 @@
 //   BT = false: B is [K,N] row-major (P V of attention)                                  -> C = A B
 //   epilogue  : v = alpha*acc; v = v*scale[n] + shift[n] (eval BatchNorm folded) | v += shift[n] (bias);
 //               v += residual[m,n]; v = max(v,0)
-// Tile 128 x BN x 32, 512 threads = 8 waves (4x2), each wave a 32 x BN/2 block of 32x32 MFMA tiles (or 256 threads,
-// 2x2 waves of 64 x BN/2); LDS tiles are
+// Tile 128 x BN x 32, 512 threads = 8 waves (4x2), each wave a 32 x BN/2 block of 32x32 MFMA tiles; LDS tiles are
 // stored k-major so an MFMA operand fetch is a conflict-free ds_read_b32 (lanes 0-31: 32 consecutive rows at k,
 // lanes 32-63: the same rows at k+1); the next k-tile is prefetched into registers while the current one is
 // multiplied.
@@ -50,18 +49,15 @@ __device__ __forceinline__ float4 load4_guarded(const float* __restrict__ p, int
   return v;
 }
 
-// WPE: waves per SIMD the register allocation must allow.  1 = unconstrained (172 registers, 2 waves): best for long K,
-// where the MFMA stream dominates; 3 (<= 168 registers): best for K <= 256, where prologue, staging and the epilogue
-// of a workgroup have to hide behind other workgroups (measured: conv 64->128 41.7 -> 48.1, Q K^T 61 -> 72 TFLOP/s,
-// but 4096^3 109.6 -> 102.6).
-// NWM: waves along M (2: 256 threads, each wave 64 x BN/2; 4: 512 threads, each wave 32 x BN/2 -- twice the MFMA
-// streams per workgroup for grids that put only one or two workgroups on a CU).
+// 512-thread workgroups (8 waves, 80 registers, up to 6 waves per SIMD): against the removed 256-thread form (4 waves, 139-172
+// registers) short-K shapes gain 15-25 % (conv 64->128: 47 -> 56, Q K^T: 73 -> 90 TFLOP/s) and the long-K ones are unchanged.
 // GUARD = false: every tile is full and 16-byte aligned (M % 128 == 0, N % BN == 0, K % 32 == 0, leading dimensions and batch
 // strides multiples of 4 floats -- checked by the launcher): the fetch is four plain global_load_dwordx4 per thread.  The guarded
 // form costs more than its bounds checks suggest: its per-lane branches compile into ~130 instructions of exec-mask juggling
 // between the second barrier and the MFMA loop of every k-tile (measured: 101.6 -> 117 TFLOP/s at 65536 x 512 x 512 without it).
-template <int BN, bool BT, int WPE, int NWM = 2, bool GUARD = true>
-__global__ __launch_bounds__(NWM * 128, WPE) void gemm_f32_kernel(GemmArgs g) {
+template <int BN, bool BT, bool GUARD>
+__global__ __launch_bounds__(512, 6) void gemm_f32_kernel(GemmArgs g) {
+  constexpr int NWM = 4;                               // waves along M
   constexpr int NT = NWM * 128;                        // threads
   constexpr int MI = BM / (32 * NWM);                  // 32-row MFMA tiles per wave along M
   constexpr int LDA = BM + 1;                         // k-major tiles, +1 breaks the transposing writes' conflicts
@@ -351,42 +347,23 @@ extern "C" int houv_gemm_f32(const float* A, const float* B, float* C, int M, in
   hipStream_t s = (hipStream_t)stream;
   const bool narrow = N <= 64;
   dim3 grid((N + (narrow ? 64 : 128) - 1) / (narrow ? 64 : 128), (M + BM - 1) / BM, outer * inner);
-  // 512-thread workgroups (8 waves, 80 registers, up to 6 waves per SIMD) everywhere: against the 256-thread form
-  // (4 waves, 139-172 registers) short-K shapes gain 15-25 % (conv 64->128: 47 -> 56, Q K^T: 73 -> 90 TFLOP/s) and the
-  // long-K ones are unchanged; houv_debug_set("gemm_4w", 1) selects the 256-thread kernels for comparison.
-  const bool four_waves = g_debug.gemm_4w.load() != 0;   // houv_debug_set: A/B diagnostics only
-  const bool short_k = K <= 256;
-  if (four_waves) {
-    if (narrow) {
-      if (trans_b) gemm_f32_kernel<64, true, 3><<<grid, 256, 0, s>>>(g);
-      else gemm_f32_kernel<64, false, 3><<<grid, 256, 0, s>>>(g);
-    } else if (short_k) {
-      if (trans_b) gemm_f32_kernel<128, true, 3><<<grid, 256, 0, s>>>(g);
-      else gemm_f32_kernel<128, false, 3><<<grid, 256, 0, s>>>(g);
-    } else {
-      if (trans_b) gemm_f32_kernel<128, true, 1><<<grid, 256, 0, s>>>(g);
-      else gemm_f32_kernel<128, false, 1><<<grid, 256, 0, s>>>(g);
-    }
+  // full, aligned tiles everywhere (every DCP shape at 2048 points): the unguarded kernels
+  const int bn = narrow ? 64 : 128;
+  const bool aligned16 = !((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) &&
+                         !((lda | ldb | (int)(sAo & 3) | (int)(sAi & 3) | (int)(sBo & 3) | (int)(sBi & 3)) & 3);
+  const bool full = aligned16 && M % BM == 0 && N % bn == 0 && K % BK == 0;
+  const int split = g_debug.gemm_split.load();               // 0: fp32-input MFMA; 6 / 3: bf16 part products (see gemm_split_kernel)
+  if (split && full && trans_b) {
+    if (narrow) { if (split == 6) gemm_split_kernel<64, 6><<<grid, 512, 0, s>>>(g); else gemm_split_kernel<64, 3><<<grid, 512, 0, s>>>(g); }
+    else { if (split == 6) gemm_split_kernel<128, 6><<<grid, 512, 0, s>>>(g); else gemm_split_kernel<128, 3><<<grid, 512, 0, s>>>(g); }
+    return check_launch("houv_gemm_f32") ? 1 : 0;
+  }
+  if (narrow) {
+    if (trans_b) { if (full) gemm_f32_kernel<64, true, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<64, true, true><<<grid, 512, 0, s>>>(g); }
+    else { if (full) gemm_f32_kernel<64, false, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<64, false, true><<<grid, 512, 0, s>>>(g); }
   } else {
-    // full, aligned tiles everywhere (every DCP shape at 2048 points): the unguarded kernels
-    const int bn = narrow ? 64 : 128;
-    const bool aligned16 = !((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) &&
-                           !((lda | ldb | (int)(sAo & 3) | (int)(sAi & 3) | (int)(sBo & 3) | (int)(sBi & 3)) & 3);
-    const bool force_guard = g_debug.gemm_guarded.load() != 0;   // diagnostics / A-B only
-    const bool full = !force_guard && aligned16 && M % BM == 0 && N % bn == 0 && K % BK == 0;
-    const int split = g_debug.gemm_split.load();               // 0: fp32-input MFMA; 6 / 3: bf16 part products (see gemm_split_kernel)
-    if (split && full && trans_b) {
-      if (narrow) { if (split == 6) gemm_split_kernel<64, 6><<<grid, 512, 0, s>>>(g); else gemm_split_kernel<64, 3><<<grid, 512, 0, s>>>(g); }
-      else { if (split == 6) gemm_split_kernel<128, 6><<<grid, 512, 0, s>>>(g); else gemm_split_kernel<128, 3><<<grid, 512, 0, s>>>(g); }
-      return check_launch("houv_gemm_f32") ? 1 : 0;
-    }
-    if (narrow) {
-      if (trans_b) { if (full) gemm_f32_kernel<64, true, 6, 4, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<64, true, 6, 4><<<grid, 512, 0, s>>>(g); }
-      else { if (full) gemm_f32_kernel<64, false, 6, 4, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<64, false, 6, 4><<<grid, 512, 0, s>>>(g); }
-    } else {
-      if (trans_b) { if (full) gemm_f32_kernel<128, true, 6, 4, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<128, true, 6, 4><<<grid, 512, 0, s>>>(g); }
-      else { if (full) gemm_f32_kernel<128, false, 6, 4, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<128, false, 6, 4><<<grid, 512, 0, s>>>(g); }
-    }
+    if (trans_b) { if (full) gemm_f32_kernel<128, true, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<128, true, true><<<grid, 512, 0, s>>>(g); }
+    else { if (full) gemm_f32_kernel<128, false, false><<<grid, 512, 0, s>>>(g); else gemm_f32_kernel<128, false, true><<<grid, 512, 0, s>>>(g); }
   }
   return check_launch("houv_gemm_f32") ? 1 : 0;
 }

@@ -26,30 +26,15 @@ inline bool check_launch(const char* what) {
 }
 
 // Diagnostic switches (houv_debug_set; tests, A/B scripts and bench.py only -- never the environment).  Results are proven
-// independent of every switch except the two that select an alternative kernel for A/B timing (chamfer_direct, gemm_*).
+// independent of every switch except the two that select the matrix-pipe kernels (gemm_split, attn_split).
 //   "solve_predict"   0 normal; 1 always predict direction B (every A-win takes the repair path); 2 rescan everything
-//   "prune_refresh"   pruned mode: every n-th iteration refreshes every remembered nearest neighbour (default 4)
-//   "prune_cap_slack" pruned walk: lock-step passes run for (mean list length of the wave + this) steps; -1 = fused loop only
-//   "solve_stats"     device address of 4 uint64 counters the fused loop's sweeps add to (0 = off): see SolveArgs::stats
-//   "prune_min_points" n: the pruned search serves clouds of n..2048 points (default 257; below, the brute-force kernel runs)
-//   "prune_owner_walk" 1: the pruned search walks its sub-tile lists by owner lanes at every size (A/B against the balanced walk)
-//   "chamfer_direct"  1: houv_chamfer_forward runs the direct sweep instead of the filtered one (same bits)
-//   "chamfer_q"       queries per lane cap of the filtered Chamfer kernel (8)
-//   "gemm_4w" / "gemm_guarded"   houv_gemm_f32: 4-wave workgroups / always the guarded tile fetch
-//   "gemm_split"      houv_gemm_f32: 0 fp32-input MFMA, 6 / 3 = bf16 part products per fp32 product (gemm.hip, gemm_split_kernel)
+//   "solve_stats"     device address of 6 uint64 counters the fused loop adds to (0 = off): see SolveArgs::stats
 //   "knn_split"       houv_knn: 1 references split over the four waves of a workgroup (same lists), 0 the single-scan kernel
 //   "attn_split"      houv_attention_f32: 1 bf16 matrix pipe with three-part splits (full tiles), 0 fp32-input MFMA kernel
+//   "gemm_split"      houv_gemm_f32: 0 fp32-input MFMA, 6 / 3 = bf16 part products per fp32 product (gemm.hip, gemm_split_kernel)
 struct DebugKnobs {
   std::atomic<int> pred_mode{0};
-  std::atomic<int> ws_refresh{4};
-  std::atomic<int> prune_cap_slack{1};   // pruned walk: lock-step passes capped at the wave's mean list length + this (< 0: off)
   std::atomic<unsigned long long> stats{0ull};
-  std::atomic<int> prune_min_points{257};  // the pruned search serves clouds of at least this many points (>= 257: two points per lane)
-  std::atomic<int> prune_owner_walk{0};  // 1: the pruned search walks its lists by owner lanes at every size (round 2's walk)
-  std::atomic<int> chamfer_direct{0};
-  std::atomic<int> chamfer_q{8};
-  std::atomic<int> gemm_4w{0};
-  std::atomic<int> gemm_guarded{0};
   std::atomic<int> knn_split{1};         // houv_knn (N >= 512, k = 16 / 20): four waves per 64 queries, a quarter of the references each; 0: one wave per 64 queries
   std::atomic<int> attn_split{1};        // houv_attention_f32 on the bf16 matrix pipe (attention.hip, attention_split_kernel); 0: fp32-input MFMA
   std::atomic<int> gemm_split{6};        // houv_gemm_f32 on the bf16 matrix pipe: 6 / 3 part products per fp32 product (0: fp32-input MFMA)

@@ -13,7 +13,7 @@ typedef const houv_f4v __attribute__((address_space(3))) * lds_f4;   // LDS poin
 // Per-lane global accesses of the fused loop go through buffer resources: a uniform base (4 SGPRs) + ONE 32-bit per-lane byte
 // offset shared by all of a lane's points + a uniform byte offset (the point's chunk k * BLOCK, the row of the workspace).  As
 // plain pointers, LLVM hoisted one 64-bit address per point and row out of the iteration loop and spilled them to scratch
-// (solve_kernel<512, 4, 4, 2, 1>: 124 of its 192 scratch reloads, 416 B per lane).  Every access is in bounds by construction
+// (solve_kernel<512, 4, 4, 2>: 124 of its 192 scratch reloads, 416 B per lane).  Every access is in bounds by construction
 // (callers guard with the same predicates as before); `bytes` is the size of the region.
 // The thread index, opaque to the optimiser at every use: whatever the fused loop derives from it per lane (offsets, LDS
 // addresses, lane masks) is recomputed where it is used, with a VALU instruction or two, instead of being hoisted out of the
@@ -225,56 +225,27 @@ __device__ __forceinline__ float4 recover_nn(const float4* __restrict__ rp, floa
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// EXACT pruned sweep (houv_solve_iterate_pruned; this first form, walked by the OWNING lanes, was round 2's and is kept for A/B --
-// the product runs pruned_sweep_sorted further down).  References are grouped in the same 32-point sub-tiles as
-// the brute-force sweep; every sub-tile carries an axis-aligned bounding box.  For every query and metric m the
-// distance to the point that was its NN in the previous iteration is an upper bound ub[m] that is attained; a sub-tile
-// whose box is farther from the query than ub[m] for every metric cannot contain any of its NNs -- nor a point tying
-// with one -- and is skipped.  The surviving sub-tiles are visited in ascending order with the same min3 / strict-<
-// bookkeeping as sweep(), so (best, btile) come out BIT-IDENTICAL to the brute-force sweep.
-//   * per-lane sub-tile lists are 64-bit masks (<= 64 sub-tiles, i.e. clouds of <= 2048 points);
-//   * lanes walk their own lists: LDS gathers, scan order XOR-rotated per lane (conflict-free, one v_xor per read),
-//     reads software-pipelined in batches of 4;
-//   * a lane's Q lists are walked back to back inside ONE loop, so a wave runs for the max over lanes of the SUMMED
-//     list lengths (measured 60 steps for 48.8 asked at 2048^2 with views) instead of the sum of per-list maxima (70).
-// Measured alternatives (profiles/r01_pruned_variants.txt): G neighbouring queries of a lane sharing one list and every
-// gathered reference (HOUV_PRUNE_OWN = HOUV_PRUNE_GROUP = 2 or 4) does fewer, fatter steps but neighbours' lists are
-// correlated, which costs more in lane imbalance than the shared reads save: 1.05 / 1.19 vs 1.04 us per hypothesis-
-// iteration.  The walk is ~60 % of the pruned iteration, the box tests ~10 %, the bounds ~2 %.
+// EXACT pruned search (houv_solve_iterate_pruned).  References are grouped in the same 32-point sub-tiles as the brute-force
+// sweep; every sub-tile carries an axis-aligned bounding box.  For every query and metric m the distance to the point that
+// was its NN in the previous iteration is an upper bound ub[m] that is attained; a sub-tile whose box is farther from the
+// query than ub[m] for every metric cannot contain any of its NNs -- nor a point tying with one -- and is skipped.  The
+// surviving sub-tiles are visited in ascending order with the same min3 / strict-< bookkeeping as sweep(), so (best, btile)
+// come out BIT-IDENTICAL to the brute-force sweep.  A query's list of sub-tiles is one 64-bit mask (<= 64 sub-tiles, i.e.
+// clouds of <= 2048 points; super-tiles of two sub-tiles up to 4096).
 // ---------------------------------------------------------------------------------------------------------------
-#ifdef HOUV_STAMPS
-// one record per workgroup (modulo kStampWgs), summed on the host: same-address global atomics from every wave at every stamp
-// serialise in L2 (the stamped build ran 2.7x slower than the product, distorting what it measures), and an LDS array would cost the
-// <512,4> variant its second workgroup per CU.  [0..15] solve.hip's phases, [16..23]: asked, steps, waves, cycles of the sweep's phases
-constexpr int kStampWgs = 4096;
-__device__ unsigned long long g_stamp_wg[kStampWgs * 24];
-#define HOUV_STAMP_ADD(i, v) atomicAdd(&g_stamp_wg[(blockIdx.x % kStampWgs) * 24 + (i)], (unsigned long long)(v))
-#define HOUV_PSTAT(i, v) HOUV_STAMP_ADD(16 + (i), v)
-#define HOUV_PSTAMP(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); if ((tid_x() & 63) == 0) HOUV_PSTAT(i, n_ - pst_); pst_ = n_; } while (0)
-#else
-#define HOUV_PSTAMP(i) do {} while (0)
-#endif
 
-// point owned by (thread, k): a lane owns Q/OWN chunks of OWN consecutive points; chunk c of all lanes covers points
-// [c*BLOCK*OWN, (c+1)*BLOCK*OWN).  OWN = 1: strided (brute-force default), OWN = Q: Q consecutive points per lane.
-template <int BLOCK, int Q, int OWN>
-__device__ __forceinline__ int pt_index(int k) {
-  static_assert(OWN >= 1 && Q % OWN == 0 && kSub % OWN == 0, "ownership chunk must divide Q and the sub-tile");
-  return (k / OWN) * (BLOCK * OWN) + tid_x() * OWN + (k % OWN);
-}
-// the uniform part of pt_index (pt_index(k) = pt_base(k) + thread index * OWN): buffer accesses take it as a uniform offset
-template <int BLOCK, int Q, int OWN>
-constexpr int pt_base(int k) { return (k / OWN) * (BLOCK * OWN) + (k % OWN); }
+// point owned by (thread, k): chunk k of all lanes covers points [k*BLOCK, (k+1)*BLOCK) (strided: coalesced loads)
+template <int BLOCK>
+__device__ __forceinline__ int pt_index(int k) { return k * BLOCK + tid_x(); }
+// the uniform part of pt_index (pt_index(k) = pt_base(k) + thread index): buffer accesses take it as a uniform offset
+template <int BLOCK>
+constexpr int pt_base(int k) { return k * BLOCK; }
 
 // Remembered nearest neighbours of the pruned search (nn_ws): per direction one record of 4 x int16 per query, the NN index of
 // metric m at int16 m, so that the bounds take ONE 8-byte load per query.  `dir_off` = byte offset of the direction's records.
 constexpr int kNnRec = 8;
 
-#ifndef HOUV_PRUNE_GROUP
-#define HOUV_PRUNE_GROUP 1
-#endif
-
-// Minima of the NMET squared distances between G queries and the 32 references of ONE sub-tile, gathered per lane, SEPARATELY for the
+// Minima of the NMET squared distances between one query and the 32 references of ONE sub-tile, gathered per lane, SEPARATELY for the
 // sub-tile's two tracking units (references 0..15 -> ta, 16..31 -> tb).  The lane's sub-tile starts at LDS byte address
 // (xa & ~511); the scan order is rotated per lane by XOR over the 16 slots of a 256-B half -- xa carries (lane & 15) << 4 in bits
 // 4..7 -- and both halves are read through one address (the second read is an immediate offset: one v_xor per TWO reads); needs the
@@ -284,13 +255,10 @@ constexpr int kNnRec = 8;
 // (ping-pong register sets; the trailing prefetch wraps around and is dropped).  Same expression trees as sweep_tile(); the order
 // inside a tracking unit does not matter to a minimum.  ta comes in holding whatever the caller threads through the first unit
 // (its running minima, or +inf); tb is set here.
-template <int G, int NMET>
-__device__ __forceinline__ void gather_tile_min(unsigned xa, const float (&cx)[G], const float (&cy)[G], const float (&cz)[G],
-                                                float (&ta)[G][NMET], float (&tb)[G][NMET]) {
+template <int NMET>
+__device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy, float cz, float (&ta)[NMET], float (&tb)[NMET]) {
 #pragma unroll
-  for (int k = 0; k < G; ++k)
-#pragma unroll
-    for (int m = 0; m < NMET; ++m) tb[k][m] = INFINITY;
+  for (int m = 0; m < NMET; ++m) tb[m] = INFINITY;
   constexpr int kBatch = 4, kHalf = kSub / 2;
   static_assert(kSub == 32 && kHalf == kTrk, "two 256-B tracking units of 16 slots");
   auto fetch = [&](float4 (&r)[kBatch], int i0) {
@@ -302,24 +270,21 @@ __device__ __forceinline__ void gather_tile_min(unsigned xa, const float (&cx)[G
       r[u + 1] = make_float4(v1.x, v1.y, v1.z, v1.w);       // second unit
     }
   };
-  auto eval2 = [&](const float4 a, const float4 c, float (&t)[G][NMET]) {   // two references of one unit
-#pragma unroll
-    for (int k = 0; k < G; ++k) {
-      const float ax = a.x - cx[k], ay = a.y - cy[k], az = a.z - cz[k];
-      const float bx = c.x - cx[k], by = c.y - cy[k], bz = c.z - cz[k];
-      if constexpr (NMET == 4) {
-        const float axx = ax * ax, ayy = ay * ay, bxx = bx * bx, byy = by * by;
-        const float a3 = __builtin_fmaf(ay, ay, axx), b3 = __builtin_fmaf(by, by, bxx);
-        const float a1 = __builtin_fmaf(az, az, ayy), b1 = __builtin_fmaf(bz, bz, byy);
-        const float a2 = __builtin_fmaf(az, az, axx), b2 = __builtin_fmaf(bz, bz, bxx);
-        const float a0 = __builtin_fmaf(az, az, a3), b0 = __builtin_fmaf(bz, bz, b3);
-        t[k][0] = min3f(t[k][0], a0, b0);
-        t[k][1] = min3f(t[k][1], a1, b1);
-        t[k][2] = min3f(t[k][2], a2, b2);
-        t[k][3] = min3f(t[k][3], a3, b3);
-      } else {
-        t[k][0] = min3f(t[k][0], metric_sqdist<0>(ax, ay, az), metric_sqdist<0>(bx, by, bz));
-      }
+  auto eval2 = [&](const float4 a, const float4 c, float (&t)[NMET]) {   // two references of one unit
+    const float ax = a.x - cx, ay = a.y - cy, az = a.z - cz;
+    const float bx = c.x - cx, by = c.y - cy, bz = c.z - cz;
+    if constexpr (NMET == 4) {
+      const float axx = ax * ax, ayy = ay * ay, bxx = bx * bx, byy = by * by;
+      const float a3 = __builtin_fmaf(ay, ay, axx), b3 = __builtin_fmaf(by, by, bxx);
+      const float a1 = __builtin_fmaf(az, az, ayy), b1 = __builtin_fmaf(bz, bz, byy);
+      const float a2 = __builtin_fmaf(az, az, axx), b2 = __builtin_fmaf(bz, bz, bxx);
+      const float a0 = __builtin_fmaf(az, az, a3), b0 = __builtin_fmaf(bz, bz, b3);
+      t[0] = min3f(t[0], a0, b0);
+      t[1] = min3f(t[1], a1, b1);
+      t[2] = min3f(t[2], a2, b2);
+      t[3] = min3f(t[3], a3, b3);
+    } else {
+      t[0] = min3f(t[0], metric_sqdist<0>(ax, ay, az), metric_sqdist<0>(bx, by, bz));
     }
   };
   auto eval = [&](float4 (&r)[kBatch]) {
@@ -350,248 +315,78 @@ __device__ __forceinline__ void take_units(float ta, float tb, int unit0, float&
 
 // Which sub-tiles each of this lane's queries must visit: the bound per metric is the distance to the point that was the
 // query's nearest neighbour in the previous iteration (`prev`, attained), the test a point-to-box distance per metric.
-template <int BLOCK, int Q, int NMET, int OWN, int L, int G>
+template <int BLOCK, int Q, int NMET>
 __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                             const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                            buf_t ws, int prev_off, int count, unsigned long long (&un)[L]) {
-#ifdef HOUV_STAMPS
-  unsigned long long pst_ = __builtin_readcyclecounter();
-#endif
-  {
-    float ub[Q][NMET];
+                                            buf_t ws, int prev_off, int count, unsigned long long (&un)[Q]) {
+  float ub[Q][NMET];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    const bool ok = pt_index<BLOCK>(k) < count;
+    // the query's record (a lane past the end of the cloud keeps index 0: its bounds are discarded below)
+    unsigned w0 = 0u, w1 = 0u;
+    const int voff = tid_x() * kNnRec, soff = prev_off + pt_base<BLOCK>(k) * kNnRec;
+    if (ok) {
+      if constexpr (NMET == 4) {
+        const auto r = __builtin_amdgcn_raw_buffer_load_b64(ws, voff, soff, 0);
+        w0 = r[0]; w1 = r[1];
+      } else {
+        w0 = __builtin_amdgcn_raw_buffer_load_b32(ws, voff, soff, 0);
+      }
+    }
+    { const float4 r = refs[w0 & 0xffffu]; ub[k][0] = metric_sqdist<0>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+    if constexpr (NMET == 4) {
+      { const float4 r = refs[w0 >> 16]; ub[k][1] = metric_sqdist<1>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      { const float4 r = refs[w1 & 0xffffu]; ub[k][2] = metric_sqdist<2>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      { const float4 r = refs[w1 >> 16]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+    }
+#pragma unroll
+    for (int m = 0; m < NMET; ++m) ub[k][m] = ok ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;   // box distances are rounded: stay conservative
+  }
+  unsigned alo[Q], ahi[Q];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) alo[k] = ahi[k] = 0u;
+  // per query and box (17 instructions; wave-uniform t: the box reads are LDS broadcasts): the box point nearest to the query is
+  // the query clamped into the box (v_med3), its offset squared per axis and summed per metric; the verdicts are collected
+  // one bit per box by shift_in, so the boxes run in DESCENDING order, 32 per mask word
+  auto test = [&](const float4 lo, const float4 hi, unsigned (&acc)[Q]) {
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
-      const bool ok = pt_index<BLOCK, Q, OWN>(k) < count;
-      // the query's record (a lane past the end of the cloud keeps index 0: its bounds are discarded below)
-      unsigned w0 = 0u, w1 = 0u;
-      const int voff = tid_x() * (OWN * kNnRec), soff = prev_off + pt_base<BLOCK, Q, OWN>(k) * kNnRec;
-      if (ok) {
-        if constexpr (NMET == 4) {
-          const auto r = __builtin_amdgcn_raw_buffer_load_b64(ws, voff, soff, 0);
-          w0 = r[0]; w1 = r[1];
-        } else {
-          w0 = __builtin_amdgcn_raw_buffer_load_b32(ws, voff, soff, 0);
-        }
-      }
-      { const float4 r = refs[w0 & 0xffffu]; ub[k][0] = metric_sqdist<0>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      const float dx = qx[k] - __builtin_amdgcn_fmed3f(qx[k], lo.x, hi.x);
+      const float dy = qy[k] - __builtin_amdgcn_fmed3f(qy[k], lo.y, hi.y);
+      const float dz = qz[k] - __builtin_amdgcn_fmed3f(qz[k], lo.z, hi.z);
+      unsigned long long in;                              // lane mask of the compares, OR-ed on the scalar unit (no branches)
       if constexpr (NMET == 4) {
-        { const float4 r = refs[w0 >> 16]; ub[k][1] = metric_sqdist<1>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
-        { const float4 r = refs[w1 & 0xffffu]; ub[k][2] = metric_sqdist<2>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
-        { const float4 r = refs[w1 >> 16]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+        const float xx = dx * dx, yy = dy * dy;
+        const float s3 = __builtin_fmaf(dy, dy, xx), s1 = __builtin_fmaf(dz, dz, yy), s2 = __builtin_fmaf(dz, dz, xx);
+        const float s0 = __builtin_fmaf(dz, dz, s3);
+        in = __builtin_amdgcn_ballot_w64(s0 <= ub[k][0]) | __builtin_amdgcn_ballot_w64(s1 <= ub[k][1]) |
+             __builtin_amdgcn_ballot_w64(s2 <= ub[k][2]) | __builtin_amdgcn_ballot_w64(s3 <= ub[k][3]);
+      } else {
+        in = __builtin_amdgcn_ballot_w64(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) <= ub[k][0]);
       }
-#pragma unroll
-      for (int m = 0; m < NMET; ++m) ub[k][m] = ok ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;   // box distances are rounded: stay conservative
+      acc[k] = shift_in_mask(acc[k], in);
     }
-    unsigned alo[L], ahi[L];
-#pragma unroll
-    for (int g = 0; g < L; ++g) alo[g] = ahi[g] = 0u;
-    HOUV_PSTAMP(3);
-    // per query and box (17 instructions; wave-uniform t: the box reads are LDS broadcasts): the box point nearest to the query is
-    // the query clamped into the box (v_med3), its offset squared per axis and summed per metric; the verdicts are collected
-    // one bit per box by shift_in, so the boxes run in DESCENDING order, 32 per mask word
-    auto test = [&](const float4 lo, const float4 hi, unsigned (&acc)[L]) {
-#pragma unroll
-      for (int g = 0; g < L; ++g) {
-        unsigned long long in = 0ull;                     // lane masks of the compares, OR-ed on the scalar unit (no branches)
-#pragma unroll
-        for (int k = g * G; k < (g + 1) * G; ++k) {
-          const float dx = qx[k] - __builtin_amdgcn_fmed3f(qx[k], lo.x, hi.x);
-          const float dy = qy[k] - __builtin_amdgcn_fmed3f(qy[k], lo.y, hi.y);
-          const float dz = qz[k] - __builtin_amdgcn_fmed3f(qz[k], lo.z, hi.z);
-          if constexpr (NMET == 4) {
-            const float xx = dx * dx, yy = dy * dy;
-            const float s3 = __builtin_fmaf(dy, dy, xx), s1 = __builtin_fmaf(dz, dz, yy), s2 = __builtin_fmaf(dz, dz, xx);
-            const float s0 = __builtin_fmaf(dz, dz, s3);
-            in |= __builtin_amdgcn_ballot_w64(s0 <= ub[k][0]) | __builtin_amdgcn_ballot_w64(s1 <= ub[k][1]) |
-                  __builtin_amdgcn_ballot_w64(s2 <= ub[k][2]) | __builtin_amdgcn_ballot_w64(s3 <= ub[k][3]);
-          } else {
-            in |= __builtin_amdgcn_ballot_w64(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) <= ub[k][0]);
-          }
-        }
-        acc[g] = shift_in_mask(acc[g], in);
-      }
-    };
-    auto run = [&](int t_first, int t_last, unsigned (&acc)[L]) {      // t_first >= t_last; the next box is in flight while this one is tested
-      float4 lo = boxes[2 * t_first], hi = boxes[2 * t_first + 1];
-      for (int t = t_first; t >= t_last; --t) {
-        const int tn = t > 0 ? t - 1 : 0;
-        const float4 nlo = boxes[2 * tn], nhi = boxes[2 * tn + 1];
-        test(lo, hi, acc);
-        lo = nlo; hi = nhi;
-      }
-    };
-    if (ntile > 32) run(ntile - 1, 32, ahi);
-    run((ntile < 32 ? ntile : 32) - 1, 0, alo);
-#pragma unroll
-    for (int g = 0; g < L; ++g) un[g] = ((unsigned long long)ahi[g] << 32) | alo[g];
-  }
-  HOUV_PSTAMP(4);
-}
-
-template <int BLOCK, int Q, int NMET, int OWN>
-__device__ __forceinline__ void pruned_sweep(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
-                                             const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                             buf_t ws, int prev_off, int count, int rot,
-                                             float (&best)[Q][NMET], int (&btile)[Q][NMET],
-                                             unsigned long long* __restrict__ stats = nullptr, int cap_slack = -1) {
-  // G queries share one sub-tile list and every gathered reference (G = 1 by default, see above); a lane's Q/G lists
-  // are walked back to back inside ONE loop (a lane moves on to its next list while others are still on their first)
-  constexpr int G = (OWN < HOUV_PRUNE_GROUP) ? OWN : HOUV_PRUNE_GROUP;
-  constexpr int L = Q / G;
-  unsigned long long un[L];
-#ifdef HOUV_STAMPS
-  unsigned long long pst_ = __builtin_readcyclecounter();
-#endif
-  prune_masks<BLOCK, Q, NMET, OWN, L, G>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
-#pragma unroll
-  for (int k = 0; k < Q; ++k)
-#pragma unroll
-    for (int m = 0; m < NMET; ++m) { best[k][m] = INFINITY; btile[k][m] = 0; }
-  int nsteps = 0;   // wave-uniform
-  if (stats) {      // selectivity counters for bench.py's executed-work accounting (houv_debug_set("solve_stats", ptr)); wave-uniform branch
-    int asked = 0;
-#pragma unroll
-    for (int g = 0; g < L; ++g) asked += __popcll(un[g]);
-    asked = wave_incl_scan_dpp(asked);
-    if ((tid_x() & 63) == 63) {
-      atomicAdd(&stats[0], (unsigned long long)asked);
-      atomicAdd(&stats[2], 1ull);
+  };
+  auto run = [&](int t_first, int t_last, unsigned (&acc)[Q]) {      // t_first >= t_last; the next box is in flight while this one is tested
+    float4 lo = boxes[2 * t_first], hi = boxes[2 * t_first + 1];
+    for (int t = t_first; t >= t_last; --t) {
+      const int tn = t > 0 ? t - 1 : 0;
+      const float4 nlo = boxes[2 * tn], nhi = boxes[2 * tn + 1];
+      test(lo, hi, acc);
+      lo = nlo; hi = nhi;
     }
-  }
-#ifdef HOUV_STAMPS
-  {
-    int asked = 0;
+  };
+  if (ntile > 32) run(ntile - 1, 32, ahi);
+  run((ntile < 32 ? ntile : 32) - 1, 0, alo);
 #pragma unroll
-    for (int g = 0; g < L; ++g) asked += __popcll(un[g]);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) asked += __shfl_xor(asked, o, 64);
-    // union over the wave's 64 lanes of list g (64 consecutive points when OWN == 1), and over all of the wave's lists
-    int uni_g = 0;
-    unsigned long long all = 0ull;
-#pragma unroll
-    for (int g = 0; g < L; ++g) {
-      unsigned long long u = un[g];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) u |= ((unsigned long long)__shfl_xor((int)(u >> 32), o, 64) << 32) | (unsigned)__shfl_xor((int)u, o, 64);
-      uni_g += __popcll(u);
-      all |= u;
-    }
-    if ((tid_x() & 63) == 0) {
-      HOUV_PSTAT(0, (unsigned long long)asked);           // sub-tile visits the wave's lanes asked for
-      HOUV_PSTAT(2, 1ull);                                // waves
-      HOUV_PSTAT(6, (unsigned long long)uni_g);           // sum over lists of the per-list wave unions
-      HOUV_PSTAT(7, (unsigned long long)__popcll(all));   // union over the whole wave
-    }
-  }
-  pst_ = __builtin_readcyclecounter();
-  unsigned long long steps_ = 0;
-#endif
-  // ---- capped lock-step passes (round 3) --------------------------------------------------------------------------
-  // Pass g: every lane walks ITS list g, all lanes in step, for `cap` steps (wave-uniform).  The query, its running minima
-  // and sub-tile ids are then compile-time registers: no "which list is this lane on" selects, and a lane whose list has
-  // run out simply re-evaluates its last sub-tile -- harmless, an evaluation can only repeat or exceed what `best` already
-  // holds (and a sub-tile that is NOT on a lane's list cannot hold a point at or below its bound), so no activity predicate
-  // either: 22 instead of ~110 bookkeeping instructions per step.  Pure lock-step (cap = the wave's longest list) needs
-  // 70 steps where the fused loop below needs 60 (lane imbalance); so the passes are CAPPED near the wave's mean list
-  // length and what is left of the long lists goes to the fused loop, whose steps cost more but are now few.
-  const int slack = cap_slack;
-  if (slack >= 0) {
-#pragma unroll
-    for (int g = 0; g < L; ++g) {
-      const int len = __popcll(un[g]);
-      const int wsum = __builtin_amdgcn_readlane(wave_incl_scan_dpp(len), 63);
-      const int wmax = __builtin_amdgcn_readlane(wave_max_to_lane63(len), 63);
-      const int cap = min(wmax, ((wsum + 63) >> 6) + slack);
-      float cx[G], cy[G], cz[G];
-#pragma unroll
-      for (int k = 0; k < G; ++k) { cx[k] = qx[g * G + k]; cy[k] = qy[g * G + k]; cz[k] = qz[g * G + k]; }
-      int t = 0;
-#pragma unroll 1
-      for (int s = 0; s < cap; ++s) {
-        const unsigned long long mm = un[g];
-        t = (mm != 0ull) ? (__ffsll((long long)mm) - 1) : t;
-        un[g] = mm & (mm - 1ull);                              // 0 stays 0
-        const unsigned xa = (unsigned)(size_t)(lds_f4)refs + (unsigned)t * (kSub * 16u) + (((unsigned)rot & 15u) << 4);
-        float ta[G][NMET], tb[G][NMET];
-#pragma unroll
-        for (int k = 0; k < G; ++k)
-#pragma unroll
-          for (int m = 0; m < NMET; ++m) ta[k][m] = best[g * G + k][m];   // the running minima threaded through the first unit
-        gather_tile_min<G, NMET>(xa, cx, cy, cz, ta, tb);
-#pragma unroll
-        for (int k = 0; k < G; ++k)
-#pragma unroll
-          for (int m = 0; m < NMET; ++m) take_units(ta[k][m], tb[k][m], 2 * t, best[g * G + k][m], btile[g * G + k][m]);
-      }
-      nsteps += cap;
-    }
-  }
-  // ---- fused loop: whatever the passes left (everything when slack < 0) ---------------------------------------------
-  for (;;) {
-    // current list of this lane: the first one that still has sub-tiles
-    unsigned long long mm = 0ull;
-    int cur = 0;
-#pragma unroll
-    for (int g = L - 1; g >= 0; --g) {
-      const bool has = un[g] != 0ull;
-      mm = has ? un[g] : mm;
-      cur = has ? g : cur;
-    }
-    if (!__any(mm != 0ull)) break;
-    ++nsteps;
-#ifdef HOUV_STAMPS
-    ++steps_;   // sub-tile steps the wave executed
-#endif
-    const bool act = mm != 0ull;
-    const int t = act ? (__ffsll((long long)mm) - 1) : 0;
-    mm = act ? (mm & (mm - 1ull)) : 0ull;
-    float cx[G], cy[G], cz[G];
-#pragma unroll
-    for (int k = 0; k < G; ++k) { cx[k] = qx[k]; cy[k] = qy[k]; cz[k] = qz[k]; }
-#pragma unroll
-    for (int g = 0; g < L; ++g) {
-      un[g] = (cur == g) ? mm : un[g];
-      if (g > 0) {
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-          cx[k] = (cur == g) ? qx[g * G + k] : cx[k];
-          cy[k] = (cur == g) ? qy[g * G + k] : cy[k];
-          cz[k] = (cur == g) ? qz[g * G + k] : cz[k];
-        }
-      }
-    }
-    const unsigned xa = (unsigned)(size_t)(lds_f4)refs + (unsigned)t * (kSub * 16u) + (((unsigned)rot & 15u) << 4);
-    float ta[G][NMET], tb[G][NMET];
-#pragma unroll
-    for (int k = 0; k < G; ++k)
-#pragma unroll
-      for (int m = 0; m < NMET; ++m) ta[k][m] = INFINITY;               // which list the lane is on is only known per lane: fresh minima
-    gather_tile_min<G, NMET>(xa, cx, cy, cz, ta, tb);
-#pragma unroll
-    for (int g = 0; g < L; ++g)
-#pragma unroll
-      for (int k = 0; k < G; ++k)
-#pragma unroll
-        for (int m = 0; m < NMET; ++m) {
-          const bool on = act && (cur == g);
-          const bool lb = tb[k][m] < ta[k][m];                          // the second unit holds the sub-tile's minimum (strictly)
-          const float tmin = lb ? tb[k][m] : ta[k][m];
-          const bool lt = on && (tmin < best[g * G + k][m]);
-          best[g * G + k][m] = lt ? tmin : best[g * G + k][m];
-          btile[g * G + k][m] = lt ? 2 * t + (lb ? 1 : 0) : btile[g * G + k][m];
-        }
-  }
-  if (stats && (tid_x() & 63) == 0) atomicAdd(&stats[1], (unsigned long long)nsteps);
-#ifdef HOUV_STAMPS
-  if ((tid_x() & 63) == 0) HOUV_PSTAT(1, steps_);
-  HOUV_PSTAMP(5);
-#endif
+  for (int k = 0; k < Q; ++k) un[k] = ((unsigned long long)ahi[k] << 32) | alo[k];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Pruned sweep, BALANCED form (round 3; solve_kernel<.., PRUNE = 2>).  The owner-walk above loses ~20 % of its steps to
-// lane imbalance (a wave runs for its longest lane) and ~25 % of its instructions to "which of my lists am I on" selects.
-// Here the walk is detached from ownership:
+// Pruned sweep, BALANCED form (round 3; solve_kernel<.., PRUNE = 2 / 3>).  Round 2's walk by the owning lanes lost ~20 % of its
+// steps to lane imbalance (a wave runs for its longest lane) and ~25 % of its instructions to "which of my lists am I on"
+// selects (removed; profiles/r03_ab_walks.txt).  Here the walk is detached from ownership:
 //   1. every thread computes the visit masks of ITS queries (prune_masks) and parks them in LDS -- in the .w lanes of the
 //      two clouds' float4 slots, which nothing else uses (8 bytes per point index: exactly one 64-bit mask);
 //   2. the workgroup's queries are counting-sorted by list length, longest first (65 bins, LDS atomics, 2 bytes per query);
@@ -626,15 +421,11 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
   static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "the bin prefix runs on one wave while another resets the block counter");
   const int tid = tid_x(), lane = tid & 63;
   unsigned long long un[Q];
-  prune_masks<BLOCK, Q, NMET, 1, Q, 1>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
-#ifdef HOUV_STAMPS
-  unsigned long long pst_ = __builtin_readcyclecounter();   // diagnostic build: [3] bounds, [4] box tests, [5] sort, [6] walk, [7] end barrier
-  if ((tid_x() & 63) == 0) HOUV_PSTAT(2, 1ull);
-#endif
+  prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
   int len[Q], rnk[Q];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int q = pt_index<BLOCK, Q, 1>(k);
+    const int q = pt_index<BLOCK>(k);
     len[k] = __popcll(un[k]);
     rnk[k] = 0;
     if (q < count) {
@@ -657,13 +448,12 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int q = pt_index<BLOCK, Q, 1>(k);
+    const int q = pt_index<BLOCK>(k);
     if (q < count) st.order[st.hist[65 + 64 - len[k]] + rnk[k]] = (unsigned short)q;
   }
   __syncthreads();
   const int nblk = (count + 63) >> 6;
   int asked = 0, nsteps = 0;
-  HOUV_PSTAMP(5);
   for (;;) {
     int b = 0;
     if (lane == 0) b = atomicAdd(&st.hist[130], 1);
@@ -675,7 +465,6 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
     unsigned long long mm = valid ? (((unsigned long long)w_slot(whi, q) << 32) | w_slot(wlo, q)) : 0ull;
     const int cap = __builtin_amdgcn_readfirstlane(__popcll(mm));      // sorted: lane 0 holds the block's longest list
     const float4 qp = qarr[q];
-    float cx[1] = {qp.x}, cy[1] = {qp.y}, cz[1] = {qp.z};
     float cb[NMET];
     int ct[NMET];
 #pragma unroll
@@ -691,12 +480,12 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
       for (int h = 0; h < (1 << TS); ++h) {
         const int ts = (t << TS) | h;                                   // sub-tile
         const unsigned xa = (unsigned)(size_t)(lds_f4)refs + (unsigned)ts * (kSub * 16u) + (((unsigned)rot & 15u) << 4);
-        float ta[1][NMET], tb[1][NMET];                                 // the running minima threaded through the first tracking unit
+        float ta[NMET], tb[NMET];                                       // the running minima threaded through the first tracking unit
 #pragma unroll
-        for (int m = 0; m < NMET; ++m) ta[0][m] = cb[m];
-        gather_tile_min<1, NMET>(xa, cx, cy, cz, ta, tb);
+        for (int m = 0; m < NMET; ++m) ta[m] = cb[m];
+        gather_tile_min<NMET>(xa, qp.x, qp.y, qp.z, ta, tb);
 #pragma unroll
-        for (int m = 0; m < NMET; ++m) take_units(ta[0][m], tb[0][m], 2 * ts, cb[m], ct[m]);
+        for (int m = 0; m < NMET; ++m) take_units(ta[m], tb[m], 2 * ts, cb[m], ct[m]);
       }
     }
     if (valid) {
@@ -714,15 +503,13 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
     if (lane == 63) atomicAdd(&stats[0], (unsigned long long)asked);
     if (lane == 0) {
       atomicAdd(&stats[1], (unsigned long long)nsteps);
-      atomicAdd(&stats[2], 1ull);                                       // one wave-sweep = 64 x Q queries, as in the owner walk
+      atomicAdd(&stats[2], 1ull);                                       // one wave-sweep = 64 x Q queries
     }
   }
-  HOUV_PSTAMP(6);
   __syncthreads();   // the workgroup's waves share one L1: its global stores above are visible to its loads below
-  HOUV_PSTAMP(7);
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int q = pt_index<BLOCK, Q, 1>(k);
+    const int q = pt_index<BLOCK>(k);
     const bool ok = q < count && len[k] > 0;                            // padding queries were never walked
     const int qq = ok ? q : 0;
     const unsigned tl = w_slot(wlo, qq);
@@ -740,32 +527,27 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
 }
 
 // Axis-aligned boxes of the 32-point sub-tiles of a cloud whose points live in this lane's registers (ownership as
-// pt_index): within a chunk a sub-tile spans 32/OWN consecutive lanes x OWN points; an in-lane min/max plus a few
-// xor-shuffles reduce it.  box[2t] = lo, box[2t+1] = hi.
-// TS = 1: boxes of SUPER-tiles of 64 points (two sub-tiles; a whole wave when OWN == 1) instead of sub-tiles.
-template <int BLOCK, int Q, int OWN, int TS = 0>
+// pt_index): within a chunk a sub-tile spans 32 consecutive lanes; a few xor-shuffles reduce it.  box[2t] = lo, box[2t+1] = hi.
+// TS = 1: boxes of SUPER-tiles of 64 points (two sub-tiles: a whole wave) instead of sub-tiles.
+template <int BLOCK, int Q, int TS = 0>
 __device__ __forceinline__ void tile_boxes(const float (&x)[Q], const float (&y)[Q], const float (&z)[Q], int count,
                                            int ntile, float4* __restrict__ box) {
   constexpr int kTile = kSub << TS;
-  static_assert(kTile / OWN <= 64, "a tile's owners must sit in one wave");
+  static_assert(kTile <= 64, "a tile's owners must sit in one wave");
 #pragma unroll
-  for (int c = 0; c < Q / OWN; ++c) {
+  for (int k = 0; k < Q; ++k) {
     float lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY;
-#pragma unroll
-    for (int o = 0; o < OWN; ++o) {
-      const int k = c * OWN + o;
-      if (pt_index<BLOCK, Q, OWN>(k) < count) {
-        lx = fminf(lx, x[k]); ly = fminf(ly, y[k]); lz = fminf(lz, z[k]);
-        hx = fmaxf(hx, x[k]); hy = fmaxf(hy, y[k]); hz = fmaxf(hz, z[k]);
-      }
+    if (pt_index<BLOCK>(k) < count) {
+      lx = fminf(lx, x[k]); ly = fminf(ly, y[k]); lz = fminf(lz, z[k]);
+      hx = fmaxf(hx, x[k]); hy = fmaxf(hy, y[k]); hz = fmaxf(hz, z[k]);
     }
 #pragma unroll
-    for (int o = 1; o < kTile / OWN; o <<= 1) {
+    for (int o = 1; o < kTile; o <<= 1) {
       lx = fminf(lx, __shfl_xor(lx, o, 64)); ly = fminf(ly, __shfl_xor(ly, o, 64)); lz = fminf(lz, __shfl_xor(lz, o, 64));
       hx = fmaxf(hx, __shfl_xor(hx, o, 64)); hy = fmaxf(hy, __shfl_xor(hy, o, 64)); hz = fmaxf(hz, __shfl_xor(hz, o, 64));
     }
-    const int t = pt_index<BLOCK, Q, OWN>(c * OWN) / kTile;
-    if ((tid_x() % (kTile / OWN)) == 0 && t < ntile) {
+    const int t = pt_index<BLOCK>(k) / kTile;
+    if ((tid_x() % kTile) == 0 && t < ntile) {
       box[2 * t] = make_float4(lx, ly, lz, 0.f);
       box[2 * t + 1] = make_float4(hx, hy, hz, 0.f);
     }

@@ -26,9 +26,6 @@
 //     hence the same bits everywhere downstream, for ~1/8 of the point pairs.
 #include <stddef.h>
 #include <stdlib.h>
-#ifdef HOUV_STAMPS
-#include <vector>
-#endif
 
 #include "../../include/houv_hip.h"
 #include "houv_common.h"
@@ -56,36 +53,19 @@ struct SolveArgs {
                      // iteration; rows 8..15 = ws_stride float4 of scratch (the balanced walk's minima per query)
   int ws_valid;      //   1: nn_ws holds the NNs of the iteration before this launch's first one
   int ws_stride;
-  int pred_mode;     // diagnostics (HOUV_SOLVE_PREDICT): 0 normal; 1 always predict direction B (every A-win takes the
+  int pred_mode;     // diagnostics (houv_debug_set("solve_predict")): 0 normal; 1 always predict direction B (every A-win takes the
                      // repair path); 2 rescan everything (no skipping: the round-1 epilogue's work)
-  int ws_refresh;    // pruned mode: every ws_refresh-th iteration rescans everything (refreshes every remembered NN)
-  int cap_slack;     // pruned walk: lock-step passes capped at the wave's mean list length + cap_slack (< 0: fused loop only)
   unsigned long long* stats;   // houv_debug_set("solve_stats", device pointer): [0] sub-tile visits the lanes of the pruned sweeps
                                // asked for, [1] sub-tile steps their waves executed, [2] pruned wave-sweeps, [3] brute wave-sweeps,
                                // [4] shader clocks (s_memtime) and [5] 100-MHz ticks (s_memrealtime) summed over the workgroups'
                                // loops: [4]/[5] x 100 MHz = the clock the chip sustained under THIS kernel's load
 };
 
-#ifdef HOUV_STAMPS
-// Diagnostic build only (scripts/stamps.sh): per-phase wave-cycle totals, never read by the kernel itself.
-#define HOUV_STAMP(i)                                                        \
-  do {                                                                       \
-    const unsigned long long now_ = __builtin_readcyclecounter();           \
-    if ((tid_x() & 63) == 0) HOUV_STAMP_ADD(i, now_ - t_stamp_);   \
-    t_stamp_ = now_;                                                         \
-  } while (0)
-#define HOUV_STAMP_PARAM , unsigned long long& t_stamp_
-#define HOUV_STAMP_ARG , t_stamp_
-#else
-#define HOUV_STAMP(i) do {} while (0)
-#define HOUV_STAMP_PARAM
-#define HOUV_STAMP_ARG
-#endif
-
-#ifndef HOUV_RESCAN_BATCH
-#define HOUV_RESCAN_BATCH 4
-#endif
-constexpr int kRescanBatch = HOUV_RESCAN_BATCH;
+constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS reads (recover_nn)
+// pruned mode: every kRefresh-th iteration rescans everything and so refreshes every remembered NN.  Same-device A/B of the
+// balanced walk (profiles/r03_ab_refresh.txt): 1 -> 0.697, 2 -> 0.667, 4 -> 0.658, 6 -> 0.657, 8 -> 0.658 us per
+// hypothesis-iteration, identical results; round 2's owner walk, whose steps cost more, preferred 2 (r02_ab_pruned_refresh.txt).
+constexpr int kRefresh = 4;
 constexpr int kAccN = 13;      // sum sqrt(d), G[3], (G p^T)[9]
 
 constexpr int kRedStride = 4 * kAccN;   // per-wave partial sums of one direction: [metric][13]
@@ -106,10 +86,10 @@ struct Smem {
   int* ctl;        // [8 + NW]
   float4* tbox;    // [2*64] lo/hi boxes of the target's 32-point sub-tiles   (pruned mode only)
   float4* mbox;    // [2*64] same for the moved cloud, rebuilt every iteration
-  SortedStage st;  // staging of the balanced pruned sweep (PRUNE == 2 only)
+  SortedStage st;  // staging of the balanced pruned sweep (pruned mode only)
 };
 
-// prune: 0 brute force, 1 pruned (owner walk), 2 pruned (balanced walk: + staging for block * q queries)
+// prune: 0 brute force, 2 pruned (balanced walk: + staging for block * q queries)
 // PRUNE == 3: the balanced walk over 64-point SUPER-tiles (pairs of sub-tiles) for clouds of 2049..4096 points: the clouds are
 // padded to multiples of 64 points
 __host__ __device__ inline int pad_unit(int prune) { return prune == 3 ? 2 * kSub : kSub; }
@@ -117,15 +97,14 @@ __host__ __device__ inline int pad_unit(int prune) { return prune == 3 ? 2 * kSu
 __host__ __device__ inline size_t smem_bytes(int N, int M, int block, int prune, int q) {
   const int pu = pad_unit(prune);
   int npad = (N + pu - 1) / pu * pu, mpad = (M + pu - 1) / pu * pu;
-  if (prune >= 2) npad = mpad = (npad > mpad ? npad : mpad);   // the balanced walk parks a mask half in EITHER cloud's .w lanes
+  if (prune) npad = mpad = (npad > mpad ? npad : mpad);   // the balanced walk parks a mask half in EITHER cloud's .w lanes
   const int nw = block / 64;
   const size_t nq = (size_t)block * q;
   return (size_t)(npad + mpad) * 16 + 28 * 8 + kPoseFloats * 4 + 8 * kAccStride * 4 + (size_t)2 * nw * kRedStride * 4 +
-         kHistSets * kHistBins * 4 + (8 + nw) * 4 + 64 + (prune ? 2 * 128 * 16 : 0) +
-         (prune >= 2 ? nq * 2 + 132 * 4 : 0);
+         kHistSets * kHistBins * 4 + (8 + nw) * 4 + 64 + (prune ? 2 * 128 * 16 + nq * 2 + 132 * 4 : 0);
 }
 
-// nq = BLOCK * Q for the balanced pruned sweep (PRUNE >= 2), 0 otherwise; pu = pad_unit(PRUNE)
+// nq = BLOCK * Q for the balanced pruned sweep (PRUNE != 0), 0 otherwise; pu = pad_unit(PRUNE)
 __device__ inline Smem carve(unsigned char* base, int N, int M, int block, int nq, int pu) {
   int npad = (N + pu - 1) / pu * pu, mpad = (M + pu - 1) / pu * pu;
   if (nq) npad = mpad = (npad > mpad ? npad : mpad);
@@ -279,7 +258,7 @@ __device__ __forceinline__ void park(float v, float* dst) {
 }
 
 // selections of one direction: bit k of bits[m] = query k of this lane takes part in metric m's mean
-template <int BLOCK, int Q, int NMET, int OWN>
+template <int BLOCK, int Q, int NMET>
 __device__ __forceinline__ void select_all(const Smem& sm, const float (&best)[Q][NMET], int count, int k_full, int k_view,
                                            int& hrot, unsigned (&bits)[NMET]) {
   bool valid[Q], sel[Q];
@@ -289,7 +268,7 @@ __device__ __forceinline__ void select_all(const Smem& sm, const float (&best)[Q
     const int ksel = (m == 0) ? k_full : k_view;     // the view terms take all points in every caller (k_view == count)
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
-      valid[k] = pt_index<BLOCK, Q, OWN>(k) < count;
+      valid[k] = pt_index<BLOCK>(k) < count;
       key[k] = valid[k] ? __float_as_uint(best[k][m]) : 0xFFFFFFFFu;
       sel[k] = valid[k];
     }
@@ -313,7 +292,7 @@ __device__ __forceinline__ float lane_sqrt_sum(const float (&bd)[Q], unsigned se
 
 // this lane's share of G[3], GP[9] for one metric: exact NN recovery + products, per query (nothing is kept per query)
 // WS: remember each query's NN for the pruned search's next bounds (metric MET's int16 of the query's record at ws + ws_off)
-template <int BLOCK, int Q, int MET, int DIR, int OWN, bool WS>
+template <int BLOCK, int Q, int MET, int DIR, bool WS>
 __device__ __forceinline__ void lane_grad_sums(const Smem& sm, const float4* __restrict__ refs, const float (&qx)[Q],
                                                const float (&qy)[Q], const float (&qz)[Q], const float (&bd)[Q],
                                                const int (&bt)[Q], unsigned selbits, int count, const float (&px)[Q],
@@ -333,9 +312,9 @@ __device__ __forceinline__ void lane_grad_sums(const Smem& sm, const float4* __r
   for (int k = 0; k < Q; ++k) {
     int jn;
     const float4 nn = recover_nn<MET, kRescanBatch, true>(refs + bt[k] * kTrk, qx[k], qy[k], qz[k], bd[k], rot, jn);
-    if (WS && pt_index<BLOCK, Q, OWN>(k) < count)
-      __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(bt[k] * kTrk + jn), ws, tid_x() * (OWN * kNnRec),
-                                            ws_off + pt_base<BLOCK, Q, OWN>(k) * kNnRec + MET * 2, 0);
+    if (WS && pt_index<BLOCK>(k) < count)
+      __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(bt[k] * kTrk + jn), ws, tid_x() * kNnRec,
+                                            ws_off + pt_base<BLOCK>(k) * kNnRec + MET * 2, 0);
     if ((selbits >> k) & 1u) {
       const float s = (bd[k] < INFINITY) ? sqrtf(bd[k]) : NAN;
       const float inv = 1.0f / s;   // d == 0 -> inf, and 0*inf = NaN below, as torch's sqrt backward gives
@@ -375,7 +354,7 @@ __device__ __forceinline__ void park_sqrt_sums(const float (&best)[Q][NMET], con
 }
 
 // G, GP of the metrics in `mask` of one direction -> red[dir][wave][m*13 + 1 ..]; no barrier in here
-template <int BLOCK, int Q, int NMET, int DIR, int OWN, bool WS>
+template <int BLOCK, int Q, int NMET, int DIR, bool WS>
 __device__ __forceinline__ void park_grad_sums(const Smem& sm, const float4* __restrict__ refs, const float (&qx)[Q],
                                                const float (&qy)[Q], const float (&qz)[Q], const float (&best)[Q][NMET],
                                                const int (&btile)[Q][NMET], const unsigned (&selbits)[NMET], unsigned mask,
@@ -389,8 +368,8 @@ __device__ __forceinline__ void park_grad_sums(const Smem& sm, const float4* __r
       bd[k] = best[k][MET];                                                                                         \
       bt[k] = btile[k][MET];                                                                                        \
     }                                                                                                               \
-    lane_grad_sums<BLOCK, Q, MET, DIR, OWN, WS>(sm, refs, qx, qy, qz, bd, bt, selbits[MET], count, px, py, pz, g,   \
-                                                ws, ws_off);                                                        \
+    lane_grad_sums<BLOCK, Q, MET, DIR, WS>(sm, refs, qx, qy, qz, bd, bt, selbits[MET], count, px, py, pz, g,        \
+                                           ws, ws_off);                                                             \
     _Pragma("unroll") for (int i = 0; i < kGradN; ++i) park(g[i], red_wave + MET * kAccN + 1 + i);                  \
   }
   HOUV_GRAD(0)
@@ -434,11 +413,11 @@ __device__ __forceinline__ unsigned picked_direction(const Smem& sm, int k_full,
 }
 
 // this lane's source point k (pt_index) of the pair's cloud `src` (N points): one buffer_load_dwordx3; 0 past the end
-template <int BLOCK, int Q, int OWN>
+template <int BLOCK>
 __device__ __forceinline__ void load_src_point(buf_t src, int k, int N, float& x, float& y, float& z) {
   x = y = z = 0.f;
-  if (pt_index<BLOCK, Q, OWN>(k) < N) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b96(src, tid_x() * (OWN * 12), pt_base<BLOCK, Q, OWN>(k) * 12, 0);
+  if (pt_index<BLOCK>(k) < N) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b96(src, tid_x() * 12, pt_base<BLOCK>(k) * 12, 0);
     x = __uint_as_float(v[0]); y = __uint_as_float(v[1]); z = __uint_as_float(v[2]);
   }
 }
@@ -446,7 +425,7 @@ __device__ __forceinline__ void load_src_point(buf_t src, int k, int N, float& x
 // Mis-prediction repair (rare): metric MET's gradient flows through direction A, but A's rescans were skipped because the
 // previous iteration's winner was B and A's sweep state is gone.  Redo A for this one metric: moved points, single-metric
 // sweep (bit-identical minima and sub-tiles: same expression tree, same tie rule), selection, rescan, sums.
-template <int BLOCK, int Q, int MET, int OWN>
+template <int BLOCK, int Q, int MET>
 __device__ __forceinline__ void repair_direction_a(const Smem& sm, buf_t src, int N, int mpad, int k_sel,
                                                    int& hrot, float* red_wave) {
   float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
@@ -457,7 +436,7 @@ __device__ __forceinline__ void repair_direction_a(const Smem& sm, buf_t src, in
   for (int i = 0; i < 3; ++i) T[i] = sm.pose[9 + i];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    load_src_point<BLOCK, Q, OWN>(src, k, N, sx[k], sy[k], sz[k]);
+    load_src_point<BLOCK>(src, k, N, sx[k], sy[k], sz[k]);
     mx[k] = __builtin_fmaf(sz[k], R[2], __builtin_fmaf(sy[k], R[1], sx[k] * R[0])) + T[0];
     my[k] = __builtin_fmaf(sz[k], R[5], __builtin_fmaf(sy[k], R[4], sx[k] * R[3])) + T[1];
     mz[k] = __builtin_fmaf(sz[k], R[8], __builtin_fmaf(sy[k], R[7], sx[k] * R[6])) + T[2];
@@ -469,30 +448,28 @@ __device__ __forceinline__ void repair_direction_a(const Smem& sm, buf_t src, in
   unsigned key[Q], bits = 0u;
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    sel[k] = pt_index<BLOCK, Q, OWN>(k) < N;
+    sel[k] = pt_index<BLOCK>(k) < N;
     key[k] = sel[k] ? __float_as_uint(bd[k]) : 0xFFFFFFFFu;
   }
   if (k_sel < N) select_smallest<BLOCK, Q>(key, k_sel, sm.hist, sm.ctl, sel, hrot);
 #pragma unroll
   for (int k = 0; k < Q; ++k) bits |= sel[k] ? (1u << k) : 0u;
   float g[kGradN];
-  lane_grad_sums<BLOCK, Q, MET, 1, OWN, false>(sm, sm.tgt, mx, my, mz, bd, bt, bits, N, sx, sy, sz, g, src, 0);
+  lane_grad_sums<BLOCK, Q, MET, 1, false>(sm, sm.tgt, mx, my, mz, bd, bt, bits, N, sx, sy, sz, g, src, 0);
 #pragma unroll
   for (int i = 0; i < kGradN; ++i) park(g[i], red_wave + MET * kAccN + 1 + i);
 }
 
-// PRUNE: the exact pruned search of houv_sweep.h.  OWN: a lane owns Q/OWN chunks of OWN consecutive points (pt_index);
-// 1 (strided, coalesced loads) everywhere by default -- other values are build-time experiments of the pruned mode
-// (HOUV_PRUNE_OWN), for which <PRUNE=false, OWN> is the brute-force sweep under the same summation order (ws_valid=-1).
+// PRUNE: 0 the brute-force sweep; 2 / 3 the exact pruned search of houv_sweep.h (balanced walk over sub-tiles / super-tiles).
 // Waves per SIMD the register budget is set for: 4 (128 VGPRs); 8 (64 VGPRs) where a lane owns one point.
-template <int BLOCK, int Q, int NMET, int PRUNE, int OWN>
+template <int BLOCK, int Q, int NMET, int PRUNE>
 __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArgs a) {
-  static_assert(PRUNE < 2 || OWN == 1, "the balanced pruned sweep keeps the strided point ownership");
+  static_assert(PRUNE == 0 || PRUNE == 2 || PRUNE == 3, "brute force, or the balanced walk over sub-tiles / super-tiles");
   constexpr int TS = (PRUNE == 3) ? 1 : 0;                      // visit masks over super-tiles of 32 << TS references
   constexpr int kPad = kSub << TS;
-  extern __shared__ __attribute__((aligned(512))) unsigned char smem_raw[];   // 512 B: pruned_sweep's XOR-rotated gathers
+  extern __shared__ __attribute__((aligned(512))) unsigned char smem_raw[];   // 512 B: the pruned walk's XOR-rotated gathers
   const int N = a.N, M = a.M;
-  const Smem sm = carve(smem_raw, N, M, BLOCK, PRUNE >= 2 ? BLOCK * Q : 0, kPad);
+  const Smem sm = carve(smem_raw, N, M, BLOCK, PRUNE ? BLOCK * Q : 0, kPad);
   const int tid = tid_x();
   const int ninst = a.P * a.K;
   // XCD-aware placement: workgroups b and b+8 share an XCD (and its L2), so give each XCD a contiguous
@@ -509,7 +486,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   for (int j = N + tid; j < npad; j += BLOCK) sm.mov[j] = pad4;
   if (tid < 24) sm.state[tid] = a.state[(size_t)inst * 24 + tid];
   for (int j = tid; j < kHistBins; j += BLOCK) sm.hist[j] = 0u;   // radix-select histogram set 0 (select_smallest rotates)
-  if constexpr (PRUNE >= 2) {
+  if constexpr (PRUNE) {
     if (tid < 132) sm.st.hist[tid] = 0;                           // list-length bins of the balanced pruned sweep
   }
   int hrot = 0;
@@ -526,11 +503,11 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     float tx0[Q], ty0[Q], tz0[Q];
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
-      const int i = pt_index<BLOCK, Q, OWN>(k);
+      const int i = pt_index<BLOCK>(k);
       const float4 v = (i < M) ? sm.tgt[i] : make_float4(0.f, 0.f, 0.f, 0.f);
       tx0[k] = v.x; ty0[k] = v.y; tz0[k] = v.z;
     }
-    tile_boxes<BLOCK, Q, OWN, TS>(tx0, ty0, tz0, M, mpad / kPad, sm.tbox);   // the target is static: boxes once per launch
+    tile_boxes<BLOCK, Q, TS>(tx0, ty0, tz0, M, mpad / kPad, sm.tbox);   // the target is static: boxes once per launch
   }
   // Adam's step-dependent scalars (two double pow()) are computed off the critical path: by thread kAdamTid (another wave,
   // hence another SIMD, when the workgroup has one) one iteration ahead, into the slot of the step's parity.
@@ -551,9 +528,6 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   }
   __syncthreads();
 
-#ifdef HOUV_STAMPS
-  unsigned long long t_stamp_ = __builtin_readcyclecounter();
-#endif
   unsigned long long clk0 = 0ull, rt0 = 0ull;   // two stamps per LAUNCH (not per iteration), only when the counters are on
   if (a.stats) {
     clk0 = __builtin_amdgcn_s_memtime();
@@ -566,7 +540,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   // is known); B's run exactly for the metrics B wins; a metric predicted B but won by A is repaired (rare).  Results do
   // not depend on the prediction.  The pruned kernel's bounds are distances to REMEMBERED nearest neighbours (nn_ws): any
   // remembered point gives a valid, attained bound, so a skipped rescan only leaves an older neighbour in place (a
-  // slightly looser bound); every ws_refresh-th iteration rescans everything to keep them fresh.
+  // slightly looser bound); every kRefresh-th iteration rescans everything to keep them fresh.
   unsigned pred_a = kAllMet;
   float* red_a = sm.red + ((size_t)1 * NW + (tid >> 6)) * kRedStride;
   float* red_b = sm.red + ((size_t)0 * NW + (tid >> 6)) * kRedStride;
@@ -575,8 +549,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     float best[Q][NMET];
     int btile[Q][NMET];
     if (a.pred_mode == 1) pred_a = 0u;
-    const bool allgrad = a.pred_mode == 2 || ((PRUNE != 0) && (a.ws_refresh <= 1 || ((a.steps_done + it) % a.ws_refresh) == 0 ||
-                                                        (a.ws_valid == 0 && it == 0)));
+    const bool allgrad = a.pred_mode == 2 || ((PRUNE != 0) && (((a.steps_done + it) % kRefresh) == 0 || (a.ws_valid == 0 && it == 0)));
     const unsigned grad_a = allgrad ? kAllMet : pred_a;
     {
       // ---- move this lane's source points, publish them as references for sweep B ----
@@ -589,9 +562,9 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       for (int i = 0; i < 3; ++i) T[i] = pose[9 + i];
 #pragma unroll
       for (int k = 0; k < Q; ++k) {
-        const int i = pt_index<BLOCK, Q, OWN>(k);
+        const int i = pt_index<BLOCK>(k);
         const bool ok = i < N;
-        load_src_point<BLOCK, Q, OWN>(src, k, N, sx[k], sy[k], sz[k]);
+        load_src_point<BLOCK>(src, k, N, sx[k], sy[k], sz[k]);
         // src @ R^T + T (houv.py:102)
         mx[k] = __builtin_fmaf(sz[k], R[2], __builtin_fmaf(sy[k], R[1], sx[k] * R[0])) + T[0];
         my[k] = __builtin_fmaf(sz[k], R[5], __builtin_fmaf(sy[k], R[4], sx[k] * R[3])) + T[1];
@@ -599,36 +572,28 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         if (ok) sm.mov[i] = make_float4(mx[k], my[k], mz[k], 0.f);
       }
       __syncthreads();
-      HOUV_STAMP(0);
       // ---- sweep A: moved -> target ----
       bool pruned_now = false;
       if constexpr (PRUNE) {
-        tile_boxes<BLOCK, Q, OWN, TS>(mx, my, mz, N, npad / kPad, sm.mbox);   // read by sweep B after the next barriers
+        tile_boxes<BLOCK, Q, TS>(mx, my, mz, N, npad / kPad, sm.mbox);   // read by sweep B after the next barriers
         pruned_now = (a.ws_valid != 0) || (it > 0);
       }
       if (pruned_now) {
-        if constexpr (PRUNE >= 2) {
+        if constexpr (PRUNE != 0)
           pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
                                               rot, sm.st, ws_res, best, btile, a.stats);
-        } else if constexpr (PRUNE == 1) {
-          pruned_sweep<BLOCK, Q, NMET, OWN>(sm.tgt, sm.tbox, mpad / kSub, mx, my, mz, ws, ws_a, N, rot, best, btile, a.stats, a.cap_slack);
-        }
       } else {
         sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
         if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
       }
-      HOUV_STAMP(1);
       // ---- epilogue A: selection, S of every metric, G/GP of the predicted-A metrics; one barrier ----
       unsigned sel[NMET];
-      select_all<BLOCK, Q, NMET, OWN>(sm, best, N, a.k_full, a.k_view, hrot, sel);
-      HOUV_STAMP(9);
+      select_all<BLOCK, Q, NMET>(sm, best, N, a.k_full, a.k_view, hrot, sel);
       park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_a);
-      park_grad_sums<BLOCK, Q, NMET, 1, OWN, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
-                                                        ws_a);
-      HOUV_STAMP(8);
+      park_grad_sums<BLOCK, Q, NMET, 1, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
+                                                   ws_a);
       __syncthreads();
       final_sums<BLOCK, NMET>(sm, 1, true, grad_a);
-      HOUV_STAMP(2);
     }
     unsigned pick_a;
     {
@@ -636,62 +601,46 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       float tx[Q], ty[Q], tz[Q];
 #pragma unroll
       for (int k = 0; k < Q; ++k) {
-        const int i = pt_index<BLOCK, Q, OWN>(k);
+        const int i = pt_index<BLOCK>(k);
         const float4 v = (i < M) ? sm.tgt[i] : make_float4(0.f, 0.f, 0.f, 0.f);
         tx[k] = v.x; ty[k] = v.y; tz[k] = v.z;
       }
       const bool pruned_now = (PRUNE != 0) && ((a.ws_valid != 0) || (it > 0));
       if (pruned_now) {
-        if constexpr (PRUNE >= 2) {
+        if constexpr (PRUNE != 0)
           pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
                                               rot, sm.st, ws_res, best, btile, a.stats);
-        } else if constexpr (PRUNE == 1) {
-          pruned_sweep<BLOCK, Q, NMET, OWN>(sm.mov, sm.mbox, npad / kSub, tx, ty, tz, ws, ws_b, M, rot, best, btile, a.stats, a.cap_slack);
-        }
       } else {
         sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
         if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
       }
-      HOUV_STAMP(3);
       // ---- epilogue B: selection and S first; then the winners are known to every thread ----
       unsigned sel[NMET];
-      select_all<BLOCK, Q, NMET, OWN>(sm, best, M, a.k_full, a.k_view, hrot, sel);
-      HOUV_STAMP(9);
+      select_all<BLOCK, Q, NMET>(sm, best, M, a.k_full, a.k_view, hrot, sel);
       park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_b);
       __syncthreads();
       final_sums<BLOCK, NMET>(sm, 0, true, 0u);
       __syncthreads();
       pick_a = picked_direction<NMET>(sm, fresh(a.k_full), fresh(a.k_view));
       const unsigned grad_b = allgrad ? kAllMet : (~pick_a & kAllMet);
-      park_grad_sums<BLOCK, Q, NMET, 0, OWN, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
-                                                        ws_b);
-      HOUV_STAMP(8);
+      park_grad_sums<BLOCK, Q, NMET, 0, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
+                                                   ws_b);
       // ---- repair: won by A, but A's rescans were skipped ----
       const unsigned miss = pick_a & ~grad_a & kAllMet;
       if (miss) {
-        if (miss & 1u) repair_direction_a<BLOCK, Q, 0, OWN>(sm, src, N, mpad, a.k_full, hrot, red_a);
+        if (miss & 1u) repair_direction_a<BLOCK, Q, 0>(sm, src, N, mpad, a.k_full, hrot, red_a);
         if constexpr (NMET == 4) {
-          if (miss & 2u) repair_direction_a<BLOCK, Q, 1, OWN>(sm, src, N, mpad, a.k_view, hrot, red_a);
-          if (miss & 4u) repair_direction_a<BLOCK, Q, 2, OWN>(sm, src, N, mpad, a.k_view, hrot, red_a);
-          if (miss & 8u) repair_direction_a<BLOCK, Q, 3, OWN>(sm, src, N, mpad, a.k_view, hrot, red_a);
+          if (miss & 2u) repair_direction_a<BLOCK, Q, 1>(sm, src, N, mpad, a.k_view, hrot, red_a);
+          if (miss & 4u) repair_direction_a<BLOCK, Q, 2>(sm, src, N, mpad, a.k_view, hrot, red_a);
+          if (miss & 8u) repair_direction_a<BLOCK, Q, 3>(sm, src, N, mpad, a.k_view, hrot, red_a);
         }
       }
       __syncthreads();
       final_sums<BLOCK, NMET>(sm, 0, false, grad_b);
       if (miss) final_sums<BLOCK, NMET>(sm, 1, false, miss);
-      HOUV_STAMP(4);
     }
-#ifdef HOUV_STAMPS
-    if (tid == 0) {   // prediction statistics: metric-iterations with A rescanned / won by A / repaired / total
-      HOUV_STAMP_ADD(12, (unsigned long long)__popc(grad_a));
-      HOUV_STAMP_ADD(13, (unsigned long long)__popc(pick_a));
-      HOUV_STAMP_ADD(14, (unsigned long long)__popc(pick_a & ~grad_a & kAllMet));
-      HOUV_STAMP_ADD(15, (unsigned long long)NMET);
-    }
-#endif
     pred_a = pick_a;
     __syncthreads();
-    HOUV_STAMP(5);
 
     // ---- per-hypothesis scalar tail: loss, closed-form gradient, Adam, next pose ----
     if (kAdamTid != 0 && tid == kAdamTid && it + 1 < a.n_iters) {   // next iteration's Adam scalars, while thread 0 works below
@@ -776,7 +725,6 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       }
     }
     __syncthreads();
-    HOUV_STAMP(6);
   }
   if (tid_x() < 24) a.state[(size_t)inst * 24 + tid_x()] = sm.state[tid_x()];   // (the prologue's address is not kept alive)
   if (a.stats) {
@@ -788,52 +736,25 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   }
 }
 
-template <int BLOCK, int Q, int PRUNE, int OWN>
+template <int BLOCK, int Q, int PRUNE>
 int launch(const SolveArgs& a, int use_views, hipStream_t s) {
   const size_t bytes = smem_bytes(a.N, a.M, BLOCK, PRUNE, Q);
   const int grid = a.P * a.K;
   hipError_t e;
   if (use_views) {
-    e = hipFuncSetAttribute((const void*)solve_kernel<BLOCK, Q, 4, PRUNE, OWN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    e = hipFuncSetAttribute((const void*)solve_kernel<BLOCK, Q, 4, PRUNE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) { set_error("houv_solve_iterate: cannot reserve %zu B of LDS: %s", bytes, hipGetErrorString(e)); return 0; }
-    solve_kernel<BLOCK, Q, 4, PRUNE, OWN><<<grid, BLOCK, bytes, s>>>(a);
+    solve_kernel<BLOCK, Q, 4, PRUNE><<<grid, BLOCK, bytes, s>>>(a);
   } else {
-    e = hipFuncSetAttribute((const void*)solve_kernel<BLOCK, Q, 1, PRUNE, OWN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    e = hipFuncSetAttribute((const void*)solve_kernel<BLOCK, Q, 1, PRUNE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) { set_error("houv_solve_iterate: cannot reserve %zu B of LDS: %s", bytes, hipGetErrorString(e)); return 0; }
-    solve_kernel<BLOCK, Q, 1, PRUNE, OWN><<<grid, BLOCK, bytes, s>>>(a);
+    solve_kernel<BLOCK, Q, 1, PRUNE><<<grid, BLOCK, bytes, s>>>(a);
   }
   return check_launch("houv_solve_iterate") ? 1 : 0;
 }
 
 }  // namespace
 }  // namespace houv
-
-#ifdef HOUV_STAMPS
-// sums of the per-workgroup stamp records (diagnostic build): first = 16 for the sweep's counters, 0 for the kernel's phases
-static int read_stamp_records(unsigned long long* host_out, int first, int n, int reset) {
-  static std::vector<unsigned long long> h(houv::kStampWgs * 24);
-  if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(houv::g_stamp_wg), h.size() * sizeof(unsigned long long)) != hipSuccess) return 0;
-  for (int i = 0; i < n; ++i) {
-    unsigned long long acc = 0ull;
-    for (int w = 0; w < houv::kStampWgs; ++w) acc += h[(size_t)w * 24 + first + i];
-    host_out[i] = acc;
-  }
-  if (reset) {
-    for (int w = 0; w < houv::kStampWgs; ++w)
-      for (int i = 0; i < n; ++i) h[(size_t)w * 24 + first + i] = 0ull;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(houv::g_stamp_wg), h.data(), h.size() * sizeof(unsigned long long)) != hipSuccess) return 0;
-  }
-  return 1;
-}
-extern "C" int houv_debug_read_prune_stats(unsigned long long* host_out, int reset) { return read_stamp_records(host_out, 16, 8, reset); }
-extern "C" int houv_debug_read_stamps(unsigned long long* host_out, int reset) { return read_stamp_records(host_out, 0, 16, reset); }
-#endif
-
-// pruned mode: consecutive points a lane owns per chunk (pt_index), for kernels with Q = 2 / Q = 4 points per lane
-#ifndef HOUV_PRUNE_OWN
-#define HOUV_PRUNE_OWN 1
-#endif
-constexpr int kOwn4 = HOUV_PRUNE_OWN;
 
 // The variant table: which solve_kernel<BLOCK, Q> serves clouds of max(N, M) points -- the SAME (BLOCK, Q) for the brute-force
 // sweep and for the pruned search, so that both sum in the same order and agree bit for bit.  Q = 3 points per lane covers
@@ -871,9 +792,10 @@ extern "C" int houv_solve_variant(int N, int M, int pruned, int* block, int* poi
   if (points_per_lane) *points_per_lane = q;
   // Up to 256 points (8 sub-tiles or fewer, one point per lane) the pruned search is not built: houv_solve_iterate_pruned then runs
   // the brute-force kernel -- the same result.  With Morton-ordered sub-tiles it did not pay up to 512 points either; with k-d leaves
-  // it does from 257 on (profiles/r03_sizes.txt: 512 points 0.119 -> 0.093 us, 320 points 0.084 -> 0.071).
-  if (prune_mode) *prune_mode = (!pruned || mx <= g_debug.prune_min_points.load() - 1) ? 0 : (mx > 2048) ? 3 :
-                               ((b == 512 && q == 4 && g_debug.prune_owner_walk.load()) ? 1 : 2);
+  // it does from 257 on (profiles/r03_sizes.txt: 512 points 0.119 -> 0.093 us, 320 points 0.084 -> 0.071).  solver.PRUNED_MIN_POINTS
+  // is the same bound.
+  constexpr int kPrunedMinPoints = 257;
+  if (prune_mode) *prune_mode = (!pruned || mx < kPrunedMinPoints) ? 0 : (mx > 2048) ? 3 : 2;
   return 1;
 }
 
@@ -904,14 +826,10 @@ static int solve_dispatch(const float* src, const float* tgt, int P, int N, int 
     set_error("%s: too many hypotheses", who);
     return 0;
   }
-  // pruned mode refreshes every remembered NN on every 4th iteration (same-device A/B with the balanced walk,
-  // profiles/r03_ab_refresh.txt: 1 -> 0.697, 2 -> 0.667, 4 -> 0.658, 6 -> 0.657, 8 -> 0.658 us per hypothesis-iteration; round 2's
-  // owner walk, whose steps cost more, preferred 2: profiles/r02_ab_pruned_refresh.txt; results identical in all).
-  // pred_mode / ws_refresh / cap_slack / stats are diagnostics set through houv_debug_set(), never through the environment.
+  // pred_mode / stats are diagnostics set through houv_debug_set(), never through the environment.
   SolveArgs a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
               lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd, nn_ws, ws_valid,
-              ws_stride, g_debug.pred_mode.load(), g_debug.ws_refresh.load(), g_debug.prune_cap_slack.load(),
-              reinterpret_cast<unsigned long long*>(g_debug.stats.load())};
+              ws_stride, g_debug.pred_mode.load(), reinterpret_cast<unsigned long long*>(g_debug.stats.load())};
   hipStream_t s = (hipStream_t)stream;
   const int mx = N > M ? N : M;
   int block = 0, q = 0, mode = 0;
@@ -933,16 +851,15 @@ static int solve_dispatch(const float* src, const float* tgt, int P, int N, int 
   // one instantiation per row of the variant table (houv_solve_variant), x {views, no views}, x {brute force, pruned}
 #define HOUV_GO(B_, Q_)                                                          \
   if (block == B_ && q == Q_) {                                                  \
-    if (mode == 2) return launch<B_, Q_, ((B_ >= 256 && Q_ >= 2) ? 2 : 0), 1>(a, use_views, s); \
-    return launch<B_, Q_, 0, 1>(a, use_views, s);                                \
+    if (mode == 2) return launch<B_, Q_, ((B_ >= 256 && Q_ >= 2) ? 2 : 0)>(a, use_views, s);    \
+    return launch<B_, Q_, 0>(a, use_views, s);                                   \
   }
   if (mx <= 2048) {
-    if (mode == 1) return launch<512, 4, 1, kOwn4>(a, use_views, s);   // round 2's owner walk, A/B only (prune_owner_walk)
     HOUV_GO(64, 1) HOUV_GO(128, 1) HOUV_GO(256, 1) HOUV_GO(256, 2) HOUV_GO(256, 3) HOUV_GO(256, 4)
     HOUV_GO(512, 3) HOUV_GO(512, 4)
   } else {
-    if (block == 1024 && q == 3) return mode == 3 ? launch<1024, 3, 3, 1>(a, use_views, s) : launch<1024, 3, 0, 1>(a, use_views, s);
-    if (block == 1024 && q == 4) return mode == 3 ? launch<1024, 4, 3, 1>(a, use_views, s) : launch<1024, 4, 0, 1>(a, use_views, s);
+    if (block == 1024 && q == 3) return mode == 3 ? launch<1024, 3, 3>(a, use_views, s) : launch<1024, 3, 0>(a, use_views, s);
+    if (block == 1024 && q == 4) return mode == 3 ? launch<1024, 4, 3>(a, use_views, s) : launch<1024, 4, 0>(a, use_views, s);
   }
 #undef HOUV_GO
   set_error("%s: no kernel variant <%d,%d>", who, block, q);

@@ -146,9 +146,8 @@ int houv_solve_iterate_large(const float* src, const float* tgt, int P, int N, i
 
 /* Which kernel variant the two entry points above launch for clouds of N and M points (host-only query, no GPU work):
  * *block = threads per workgroup (256 / 512 / 1024), *points_per_lane = query points a lane owns (1..4), *prune_mode =
- * 0 brute-force sweep, 1 pruned search walked by the owning lanes, 2 / 3 pruned search with the balanced (sorted-block) walk over
- * 32-point sub-tiles / 64-point super-tiles --
- * the template arguments of houv::solve_kernel<block, points_per_lane, metrics, prune_mode, 1>.  Any out pointer may be NULL.
+ * 0 brute-force sweep, 2 / 3 pruned search with the balanced (sorted-block) walk over 32-point sub-tiles / 64-point super-tiles --
+ * the template arguments of houv::solve_kernel<block, points_per_lane, metrics, prune_mode>.  Any out pointer may be NULL.
  * Returns 0 with houv_last_error() set when no variant serves the size (max(N,M) > 4096).
  * No counterpart in the reference (its kernel has one fixed launch shape, chamfer3D.cu:142-143); exported so that
  * the test-suite can prove that every variant is compared with the CPU oracle. */

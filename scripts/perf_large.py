@@ -1,6 +1,6 @@
 """Time per hypothesis-iteration of the fused loop for large clouds (houv_solve_iterate_large) against the un-fused path it
 replaces (solver._run_stage_unfused: Chamfer op + torch.topk + autograd + torch.optim.Adam) and, at 4096 points, against the
-in-LDS brute-force kernel (solve_kernel<1024, 4, 4, 0, 1>), at 4096 / 6144 / 8192 / 16384 points with the view terms on.
+in-LDS brute-force kernel (solve_kernel<1024, 4, 4, 0>), at 4096 / 6144 / 8192 / 16384 points with the view terms on.
 HIP events after a warm-up; the median of the repeats.  Also derives the per-CU point-pair rate solver.LARGE_PAIRS_PER_S_PER_CU
 is set from, and (--bound) runs run_stage on 256 pairs x K = 64 x 16384 points with LAUNCH_LOG on, reporting the longest launch.
 

@@ -42,3 +42,27 @@ def test_cpu_tensors_are_refused():
     from houv_amd.metrics import cd
     with pytest.raises(_lib.HouvHipError):
         cd()(torch.rand(1, 4, 3), torch.rand(1, 5, 3))
+
+
+def test_debug_switch_table_rejects_removed_switches_and_bad_gemm_split():
+    """houv_debug_set accepts only the switches that still select something, and gemm_split only the part-product counts the
+    GEMM has kernels for (0, 3, 6): anything else fails with houv_last_error set instead of silently running another kernel."""
+    from houv_amd import _lib
+    # the retired switches, each with a value the old table accepted
+    retired = {"prune": {"refresh": 4, "cap_slack": 1, "owner_walk": 1, "min_points": 300},
+               "chamfer": {"direct": 1, "q": 4}, "gemm": {"4w": 1, "guarded": 1}}
+    for prefix, switches in retired.items():
+        for suffix, value in switches.items():
+            name = f"{prefix}_{suffix}"
+            with pytest.raises(_lib.HouvHipError):
+                _lib.debug_set(name, value)
+            assert name in _lib.last_error()
+    try:
+        for value in (1, 2, 4, 5):
+            with pytest.raises(_lib.HouvHipError):
+                _lib.debug_set("gemm_split", value)
+            assert f"gemm_split = {value}" in _lib.last_error()
+        for value in (0, 3, 6):
+            _lib.debug_set("gemm_split", value)
+    finally:
+        _lib.debug_set("gemm_split", 6)

@@ -1,6 +1,6 @@
 """CPU test: the register budget of the fused loop's pruned kernels, read from the built library's gfx950 code objects.
 
-The pruned solve_kernel<BLOCK, Q, 4, 2, 1> variants (the product default for clouds of 257..2048 points; <512, 4, 4, 2, 1> is
+The pruned solve_kernel<BLOCK, Q, 4, 2> variants (the product default for clouds of 257..2048 points; <512, 4, 4, 2> is
 what bench.py times) run at 4 waves per SIMD with 128 VGPRs and must not spill: a spilled value is reloaded from scratch in
 front of a global or LDS access on every iteration.  The metadata of every kernel is in the AMDGPU notes of the code objects
 in the library's .hip_fatbin section (one offload bundle per translation unit).  Skips when the library or the LLVM tools
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "houv_amd", "lib", "libhouv_hip.so")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-KERNEL_RE = re.compile(r"solve_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E")
+KERNEL_RE = re.compile(r"solve_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EE")
 
 def _tool(name):
     for d in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"), "/opt/rocm/llvm/bin"):
@@ -53,10 +53,10 @@ def _kernel_metadata(tmp_path):
     return kernels
 
 
-def test_pruned_solve_kernels_do_not_spill(tmp_path):
+def test_pruned_four_argument_solve_kernels_do_not_spill(tmp_path):
     kernels = _kernel_metadata(tmp_path)
-    pruned = {k: v for k, v in kernels.items() if k[2] == 4 and k[3] == 2 and k[4] == 1}
-    assert (512, 4, 4, 2, 1) in pruned and (256, 3, 4, 2, 1) in pruned, sorted(kernels)
+    pruned = {k: v for k, v in kernels.items() if k[2] == 4 and k[3] == 2}
+    assert (512, 4, 4, 2) in pruned and (256, 3, 4, 2) in pruned, sorted(kernels)
     for k, f in sorted(pruned.items()):
         name = "solve_kernel<%s>" % ", ".join(map(str, k))
         assert int(f["private_segment_fixed_size"]) == 0, f"{name}: {f['private_segment_fixed_size']} B of scratch per lane"
@@ -64,13 +64,13 @@ def test_pruned_solve_kernels_do_not_spill(tmp_path):
         assert int(f["vgpr_count"]) <= 128, f"{name}: {f['vgpr_count']} VGPRs (4 waves per SIMD need <= 128)"
 
 
-def test_every_pruned_solve_kernel_is_spill_free(tmp_path):
-    """The rest of the pruned family -- the single-metric twins (NMET = 1), the 1024-thread super-tile walk (PRUNE = 3) for
-    2049..4096 points and round 2's owner walk (PRUNE = 1, A/B only) -- has no scratch either.  The brute-force sweeps
+def test_every_pruned_four_argument_solve_kernel_is_spill_free(tmp_path):
+    """The rest of the pruned family -- the single-metric twins (NMET = 1) and the 1024-thread super-tile walk (PRUNE = 3) for
+    2049..4096 points -- has no scratch either.  The brute-force sweeps
     (PRUNE = 0) are not checked: the one-point-per-lane variants run 8 waves per SIMD on 64 VGPRs and spill by design."""
     kernels = _kernel_metadata(tmp_path)
     others = {k: v for k, v in kernels.items() if k[3] != 0 and not (k[2] == 4 and k[3] == 2)}
-    assert (1024, 4, 4, 3, 1) in others and (512, 4, 1, 2, 1) in others, sorted(kernels)
+    assert (1024, 4, 4, 3) in others and (512, 4, 1, 2) in others, sorted(kernels)
     for k, f in sorted(others.items()):
         name = "solve_kernel<%s>" % ", ".join(map(str, k))
         assert int(f["private_segment_fixed_size"]) == 0, f"{name}: {f['private_segment_fixed_size']} B of scratch per lane"
