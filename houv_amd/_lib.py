@@ -53,6 +53,9 @@ _SIGNATURES = {
     "houv_furthest_point_sample": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _c_f]),
     "houv_knn_cross": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_gather_points": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _c_f]),
+    "houv_emd_forward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _flt, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "houv_emd_workspace_bytes": (ctypes.c_longlong, [_int, _int]),
+    "houv_emd_backward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _c_f, _c_f, _c_f, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

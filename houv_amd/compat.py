@@ -2,7 +2,7 @@
 
 The reference's drivers do (registration/train_HOUV.py:26-38, model_utils_completion.py:17-18)
 
-    sys.path.append("../utils"); from metrics import cd
+    sys.path.append("../utils"); from metrics import cd, fscore, emd
     from models.houv import HOUV, predict_model, solve_model
     from train_utils import solve, rotation_error, translation_error, rmse_loss, AverageValueMeter
     from model_utils import SVDHead

@@ -1,10 +1,10 @@
-"""Loss glue on top of ``metrics.cd``: the hot-path slice of registration/model_utils_completion.py
-(calc_cd :69-80, calc_cd_percent :83-100, calc_cd_percent_aligned :103-117, loss_view :157-166).
+"""Loss glue on top of ``metrics.cd`` and ``metrics.emd``: the hot-path slice of registration/model_utils_completion.py
+(calc_cd :69-80, calc_cd_percent :83-100, calc_cd_percent_aligned :103-117, loss_view :157-166, calc_emd :170-175).
 These are the un-fused, differentiable forms (one Chamfer launch + torch.topk each); the optimisation
 loop itself never calls them -- it runs inside houv_solve_iterate."""
 import torch
 
-from .metrics import cd
+from .metrics import cd, emd
 
 
 def _f1(dist1, dist2, threshold=0.0001):
@@ -44,3 +44,9 @@ def loss_view(src, tgt, dim=0, percent=1):
     keep = torch.ones((1, 1, 3), dtype=src.dtype, device=src.device)
     keep[:, :, dim] = 0
     return calc_cd_percent(src * keep, tgt * keep, percent=percent)
+
+
+def calc_emd(output, gt, eps=0.005, iterations=50):
+    """Mean EMD point distance per cloud: sqrt of the auction's squared distances, averaged (:170-175)."""
+    dist, _ = emd()(output, gt, eps, iterations)
+    return torch.sqrt(dist).mean(1)

@@ -224,6 +224,63 @@ def icp_refine(src, tgt, init=None, max_correspondence_distance=0.02, max_iterat
     return dict(T=T, fitness=fit, inlier_rmse=rmse, iterations=iters)
 
 
+def emd_workspace(B, N, device):
+    """The workspace houv_emd_forward needs for B clouds of N points (uint8, houv_emd_workspace_bytes), None when it needs none
+    (N <= 4096)."""
+    n = _lib.load().houv_emd_workspace_bytes(int(B), int(N))
+    return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
+
+
+def emd_forward(xyz1, xyz2, eps, iters, workspace=None):
+    """Auction EMD (houv_emd_forward; the reference's ``emd.forward``, utils/metrics/EMD/emd_cuda.cu, made exact).
+    xyz1[B,N,3] (bidders, the prediction), xyz2[B,N,3] (objects, the ground truth), any float dtype and layout: converted to
+    contiguous fp32 as the reference does.  Returns (dist[B,N] squared distances fp32, assignment[B,N] int32,
+    iters_run[B] int32).  Clouds above 4096 points take a workspace: ``workspace`` or one allocated here with torch."""
+    _lib.require_gpu(xyz1.contiguous(), xyz2.contiguous())
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 3 or xyz2.shape[2] != 3 or xyz1.shape[0] != xyz2.shape[0]:
+        raise _lib.HouvHipError("emd_forward: expected xyz1[B,N,3], xyz2[B,N,3]")
+    xyz1 = xyz1.contiguous().to(_F32)
+    xyz2 = xyz2.contiguous().to(_F32)
+    B, N, _ = xyz1.shape
+    M = xyz2.shape[1]
+    dev = xyz1.device
+    dist = torch.empty((B, N), dtype=_F32, device=dev)
+    assignment = torch.empty((B, N), dtype=_I32, device=dev)
+    iters_run = torch.empty((B,), dtype=_I32, device=dev)
+    if workspace is None and N == M:
+        workspace = emd_workspace(B, N, dev)
+    if workspace is not None:
+        _lib.require_gpu(workspace, xyz1)
+        need = _lib.load().houv_emd_workspace_bytes(int(B), int(N))
+        if workspace.numel() * workspace.element_size() < need:
+            raise _lib.HouvHipError(f"emd_forward: the workspace holds fewer than the {need} bytes needed")
+    with torch.cuda.device(dev):
+        ok = _lib.load().houv_emd_forward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, N, M, float(eps), int(iters), _lib.ptr(dist),
+                                          _lib.ptr(assignment), _lib.ptr(iters_run), _lib.ptr(workspace),
+                                          _lib.stream_of(xyz1))
+    _lib.check(ok, "houv_emd_forward")
+    return dist, assignment, iters_run
+
+
+def emd_backward(xyz1, xyz2, graddist, assignment):
+    """Gradient of emd_forward's dist for xyz1 (houv_emd_backward; the reference's ``emd.backward``):
+    (2 * graddist) * (xyz1 - xyz2[assignment]), fp32 [B,N,3].  The reference returns zeros for xyz2."""
+    xyz1 = xyz1.contiguous().to(_F32)
+    xyz2 = xyz2.contiguous().to(_F32)
+    graddist = graddist.contiguous().to(_F32)
+    _lib.require_gpu(xyz1, xyz2, graddist, assignment)
+    _want(assignment, _I32, "assignment")
+    B, N, _ = xyz1.shape
+    if xyz2.shape != xyz1.shape or graddist.numel() != B * N or assignment.numel() != B * N:
+        raise _lib.HouvHipError("emd_backward: shape mismatch")
+    gradxyz1 = torch.zeros_like(xyz1)
+    with torch.cuda.device(xyz1.device):
+        ok = _lib.load().houv_emd_backward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, N, _lib.ptr(graddist), _lib.ptr(assignment),
+                                           _lib.ptr(gradxyz1), _lib.stream_of(xyz1))
+    _lib.check(ok, "houv_emd_backward")
+    return gradxyz1
+
+
 # ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------
@@ -252,6 +309,8 @@ def register_torch_ops():
                "float relative_fitness, float relative_rmse) -> (Tensor, Tensor, Tensor, Tensor)")
     lib.define("pose_forward(Tensor params, int angle_base, int trans_mode, Tensor? src) -> (Tensor, Tensor, Tensor)")
     lib.define("kd_sort(Tensor cloud, int leaf, str rule) -> (Tensor, Tensor)")
+    lib.define("emd_forward(Tensor xyz1, Tensor xyz2, float eps, int iters) -> (Tensor, Tensor, Tensor)")
+    lib.define("emd_backward(Tensor xyz1, Tensor xyz2, Tensor graddist, Tensor assignment) -> Tensor")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
     lib.impl("kabsch", kabsch, "CUDA")
@@ -272,6 +331,8 @@ def register_torch_ops():
     def _kd_sort(cloud, leaf, rule):
         return kd_sort(cloud, leaf, rule, return_order=True)
     lib.impl("kd_sort", _kd_sort, "CUDA")
+    lib.impl("emd_forward", emd_forward, "CUDA")
+    lib.impl("emd_backward", emd_backward, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

@@ -247,6 +247,38 @@ int houv_knn_cross(const float* query, const float* ref, int B, int N, int M, in
 /* gather_points (utils/mm3d_pn2/ops/gather_points/gather_points.py:14-35): out[B,C,M] = features[B,C,idx[B,M]]. */
 int houv_gather_points(const float* features, const int32_t* idx, int B, int C, int N, int M, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Earth mover's distance by the auction algorithm.
+ * Replaces: pybind `emd.forward` / `emd.backward` (utils/metrics/EMD/emd.cpp, emd_cuda.cu; emd_module.py:54-95), with the
+ * reference's semantics made exact where its award step races.  xyz1[B,N,3] are the bidders ("the prediction"), xyz2[B,M,3]
+ * the objects ("the ground truth"); N == M in 1..16384, any B, eps > 0 (finite), iters >= 1.
+ * Per cloud: price[j] = 0, assign[i] = -1, owner[j] = -1; for t = 0 .. iters-1:
+ *   U = { i : assign[i] == -1 }; U empty -> stop (exact: later iterations change nothing);
+ *   bid: v_ij = (3.0f - sqrtf((dx*dx + dy*dy) + dz*dz)) - price[j], d = xyz2[j] - xyz1[i], fp32, no contraction, sqrtf
+ *        correctly rounded; j* = argmax_j v_ij (lowest j on ties); second = max_{j != j*} v_ij (= best when N == 1);
+ *        inc_i = (best - second) + eps;
+ *   award: each object that received bids goes to the largest inc, ties to the lowest i.  t < iters-1: the previous owner
+ *        is evicted (assign = -1), owner[j] = winner, assign[winner] = j, price[j] += inc_winner.  t == iters-1: every
+ *        bidder in U takes its bid object, no eviction (complete, not necessarily a bijection, as in the reference).
+ * Outputs: dist[B,N] = (dx*dx + dy*dy) + dz*dz with d = xyz1[i] - xyz2[assignment[i]] (SQUARED distance, reference
+ * CalcDist); assignment[B,N] int32; iters_run[B] (may be NULL) the iterations each cloud actually ran (< iters: the auction
+ * finished before the forced last step).
+ * N <= 4096 runs entirely in LDS and takes no workspace; 4097..16384 needs a caller-allocated device workspace of
+ * houv_emd_workspace_bytes(B, N) bytes (no alignment beyond 4 bytes; its contents on entry are ignored).  Nothing is allocated
+ * in here.  Results are deterministic: bit-identical from call to call and to the sequential restatement of this contract.
+ * Returns 0 with houv_last_error() set, launching nothing, when a check fails. */
+int houv_emd_forward(const float* xyz1, const float* xyz2, int B, int N, int M, float eps, int iters, float* dist,
+                     int32_t* assignment, int32_t* iters_run_or_null, void* workspace_or_null, void* stream);
+
+/* Bytes of the workspace houv_emd_forward needs for B clouds of N points: 0 for N <= 4096 (and for arguments out of range). */
+long long houv_emd_workspace_bytes(int B, int N);
+
+/* Replaces: pybind `emd.backward` (emd_cuda.cu NmDistanceGradKernel).  ACCUMULATES into gradxyz1[B,N,3], which the caller
+ * must have zero-filled: gradxyz1[b,i] += (2*graddist[b,i]) * (xyz1[b,i] - xyz2[b,assignment[b,i]]).  The gradient of xyz2
+ * is zero, as the reference returns; nothing is written for it.  1 <= N <= 16384. */
+int houv_emd_backward(const float* xyz1, const float* xyz2, int B, int N, const float* graddist, const int32_t* assignment,
+                      float* gradxyz1, void* stream);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
