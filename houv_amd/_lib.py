@@ -53,6 +53,10 @@ _SIGNATURES = {
     "houv_furthest_point_sample": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _c_f]),
     "houv_knn_cross": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_gather_points": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _c_f]),
+    "houv_ball_query": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _flt, _flt, _int, _c_f, _c_f, _c_f]),
+    "houv_three_interpolate": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int, _int, _c_f, _c_f]),
+    "houv_scatter_points_grad": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
+    "houv_scatter_points_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
     "houv_emd_forward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _flt, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_emd_workspace_bytes": (ctypes.c_longlong, [_int, _int]),
     "houv_emd_backward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _c_f, _c_f, _c_f, _c_f]),

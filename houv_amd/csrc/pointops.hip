@@ -63,10 +63,13 @@ __global__ __launch_bounds__(BLOCK) void fps_kernel(const float* __restrict__ xy
   }
 }
 
-// k nearest points of ref[B,M,3] for every query[B,N,3] (k <= 8): sorted ascending, squared distances out.
+// k nearest points of ref[B,M,3] for every query[B,N,3]: sorted ascending, squared distances out.  The list holds K entries and
+// the first kout <= K are written (rows of kout): the insertion is a stable sort by (distance, index), so the first kout entries
+// of the K-list ARE the kout-list.
 template <int K>
 __global__ __launch_bounds__(256) void knn_cross_kernel(const float* __restrict__ query, const float* __restrict__ ref,
-                                                        int N, int M, float* __restrict__ dist2, int* __restrict__ idx) {
+                                                        int N, int M, int kout, float* __restrict__ dist2,
+                                                        int* __restrict__ idx) {
   __shared__ float4 s_ref[1024];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int qi = blockIdx.x * 256 + tid;
@@ -101,8 +104,10 @@ __global__ __launch_bounds__(256) void knn_cross_kernel(const float* __restrict_
   if (ok) {
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-      dist2[((size_t)b * N + qi) * K + j] = bd[j];
-      idx[((size_t)b * N + qi) * K + j] = bi[j];
+      if (j < kout) {
+        dist2[((size_t)b * N + qi) * kout + j] = bd[j];
+        idx[((size_t)b * N + qi) * kout + j] = bi[j];
+      }
     }
   }
 }
@@ -115,7 +120,8 @@ constexpr int kCrossQueue = 8;
 
 template <int K>
 __global__ __launch_bounds__(256) void knn_cross_queued_kernel(const float* __restrict__ query, const float* __restrict__ ref,
-                                                               int N, int M, float* __restrict__ dist2, int* __restrict__ idx) {
+                                                               int N, int M, int kout, float* __restrict__ dist2,
+                                                               int* __restrict__ idx) {
   __shared__ float4 s_ref[1024];
   __shared__ float2 s_q[kCrossQueue][256];   // [slot][lane]: (distance, index bits)
   const int b = blockIdx.y, tid = threadIdx.x;
@@ -167,8 +173,10 @@ __global__ __launch_bounds__(256) void knn_cross_queued_kernel(const float* __re
   if (ok) {
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-      dist2[((size_t)b * N + qi) * K + j] = bd[j];
-      idx[((size_t)b * N + qi) * K + j] = bi[j];
+      if (j < kout) {
+        dist2[((size_t)b * N + qi) * kout + j] = bd[j];
+        idx[((size_t)b * N + qi) * kout + j] = bi[j];
+      }
     }
   }
 }
@@ -206,18 +214,20 @@ extern "C" int houv_furthest_point_sample(const float* xyz, int B, int N, int np
 extern "C" int houv_knn_cross(const float* query, const float* ref, int B, int N, int M, int k, float* dist2,
                               int32_t* idx, void* stream) {
   using namespace houv;
-  if (B < 0 || N <= 0 || M <= 0 || k > M) {
-    set_error("houv_knn_cross: bad argument B=%d N=%d M=%d k=%d", B, N, M, k);
+  if (B < 0 || N <= 0 || M <= 0 || k < 1 || k > 32 || k > M) {
+    set_error("houv_knn_cross: bad argument B=%d N=%d M=%d k=%d (k must be in 1..32 and <= M)", B, N, M, k);
     return 0;
   }
   if (B == 0) return 1;
   if (!query || !ref || !dist2 || !idx) { set_error("houv_knn_cross: null pointer"); return 0; }
   dim3 grid((N + 255) / 256, B);
   hipStream_t s = (hipStream_t)stream;
-  if (k == 3) knn_cross_kernel<3><<<grid, 256, 0, s>>>(query, ref, N, M, dist2, idx);
-  else if (k == 1) knn_cross_kernel<1><<<grid, 256, 0, s>>>(query, ref, N, M, dist2, idx);
-  else if (k == 8) knn_cross_queued_kernel<8><<<grid, 256, 0, s>>>(query, ref, N, M, dist2, idx);
-  else { set_error("houv_knn_cross: k must be 1, 3 or 8 (got %d)", k); return 0; }
+  // the next list size up: 1, 3 (bubble) and 8, 16, 32 (queued insertions); the first k entries are written
+  if (k == 1) knn_cross_kernel<1><<<grid, 256, 0, s>>>(query, ref, N, M, k, dist2, idx);
+  else if (k <= 3) knn_cross_kernel<3><<<grid, 256, 0, s>>>(query, ref, N, M, k, dist2, idx);
+  else if (k <= 8) knn_cross_queued_kernel<8><<<grid, 256, 0, s>>>(query, ref, N, M, k, dist2, idx);
+  else if (k <= 16) knn_cross_queued_kernel<16><<<grid, 256, 0, s>>>(query, ref, N, M, k, dist2, idx);
+  else knn_cross_queued_kernel<32><<<grid, 256, 0, s>>>(query, ref, N, M, k, dist2, idx);
   return check_launch("houv_knn_cross") ? 1 : 0;
 }
 

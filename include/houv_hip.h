@@ -239,13 +239,42 @@ int houv_softmax_corr(const float* scores, int P, int N, int M, const float* pts
  * starting from point 0, each next sample = the point furthest from the chosen set (lowest index on ties). */
 int houv_furthest_point_sample(const float* xyz, int B, int N, int npoint, int32_t* idx, void* stream);
 
-/* three_nn generalised (utils/mm3d_pn2/ops/interpolate/three_nn.py:11-37): the k (1, 3 or 8) nearest points of ref[B,M,3]
- * for every query[B,N,3], nearest first: dist2[B,N,k] SQUARED distances, idx[B,N,k]. */
+/* three_nn generalised (utils/mm3d_pn2/ops/interpolate/three_nn.py:11-37): the k (1..32, k <= M) nearest points of
+ * ref[B,M,3] for every query[B,N,3], nearest first (the lower index first among equal distances): dist2[B,N,k] SQUARED
+ * distances, idx[B,N,k].  k = 1, 3, 8 have kernels of their own; any other k runs the next list size up (3, 8, 16, 32) and
+ * writes its first k entries, which are the k-list. */
 int houv_knn_cross(const float* query, const float* ref, int B, int N, int M, int k, float* dist2, int32_t* idx,
                    void* stream);
 
 /* gather_points (utils/mm3d_pn2/ops/gather_points/gather_points.py:14-35): out[B,C,M] = features[B,C,idx[B,M]]. */
 int houv_gather_points(const float* features, const int32_t* idx, int B, int C, int N, int M, float* out, void* stream);
+
+/* ball_query (utils/mm3d_pn2/ops/ball_query/src/ball_query_cuda.cu:11-54).  For every centre center[b,c] the points xyz[b,k],
+ * k = 0..N-1 in index order, are tested with d2 = ((cx-x)*(cx-x) + (cy-y)*(cy-y)) + (cz-z)*(cz-z) (fp32, no contraction): a
+ * point is a hit iff d2 == 0 || (d2 >= min_radius*min_radius && d2 < max_radius*max_radius), the radii squared in fp32.  The
+ * first nsample hits go to idx[b,c,0..] in index order; unused slots repeat the first hit; with no hit every slot is 0 (every
+ * slot is written here: the output need not be zero-filled).  cnt_or_null[b,c] = the number of hits, capped at nsample.
+ * 1 <= N, 1 <= nsample <= 64, min_radius < max_radius. */
+int houv_ball_query(const float* xyz, const float* center, int B, int N, int Mc, float min_radius, float max_radius,
+                    int nsample, int32_t* idx, int32_t* cnt_or_null, void* stream);
+
+/* three_interpolate forward (utils/mm3d_pn2/ops/interpolate/src/three_interpolate_cuda.cu): features[B,C,M], idx[B,N,3] in
+ * [0,M), weight[B,N,3] -> out[b,c,i] = (w0*f[idx0] + w1*f[idx1]) + w2*f[idx2] with f = features[b,c]. */
+int houv_three_interpolate(const float* features, const int32_t* idx, const float* weight, int B, int C, int M, int N,
+                           float* out, void* stream);
+
+/* The backward pass of gather_points (S = 1, idx[B,M]), grouping_operation (S = 1, idx[B,npoint*nsample]) and
+ * three_interpolate (S = 3, idx and weight viewed as [B,N*3]): grad_out[B,C,M/S], idx[B,M] in [0,N), weight_or_null[B,M] ->
+ * grad_features[b,c,k] = the fp32 sum, over m ASCENDING with idx[b,m] == k, of grad_out[b,c,m/S] * weight[b,m] (the product
+ * first; no weight: the term is grad_out itself), the additions sequential in that order starting from the first term.
+ * Every element of grad_features is written, 0 where nothing lands.  No float atomics: the result is bit-identical from call
+ * to call and to the sequential host loop.  An idx outside [0,N) contributes nothing.  `workspace` is caller-allocated device
+ * memory of houv_scatter_points_workspace_bytes(B, N, M) bytes (4-byte aligned; contents on entry ignored).  M % S == 0. */
+int houv_scatter_points_grad(const float* grad_out, const int32_t* idx, const float* weight_or_null, int B, int C, int N,
+                             int M, int S, float* grad_features, void* workspace, void* stream);
+
+/* Bytes of the workspace houv_scatter_points_grad needs (0 for arguments out of range). */
+long long houv_scatter_points_workspace_bytes(int B, int N, int M);
 
 /* ---------------------------------------------------------------------------------------------
  * Earth mover's distance by the auction algorithm.
