@@ -381,8 +381,9 @@ extern "C" int houv_edgeconv1(const float* xyz, const int32_t* idx, int B, int N
 
 extern "C" int houv_max_over_k(const float* act, long long npts, int k, int C, float* out, int ldo, void* stream) {
   using namespace houv;
-  if (npts <= 0 || k <= 0 || C <= 0 || (C & 3) || (ldo & 3) || !act || !out) {
-    set_error("houv_max_over_k: bad argument (C and ldo must be multiples of 4)");
+  if (npts <= 0 || k <= 0 || C <= 0 || (C & 3) || (ldo & 3) || ldo < C || !act || !out ||
+      ((reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(out)) & 15)) {
+    set_error("houv_max_over_k: bad argument (C and ldo must be multiples of 4, ldo >= C, act and out 16-byte aligned)");
     return 0;
   }
   max_over_k_kernel<<<grid_for((size_t)npts * (C / 4)), 256, 0, (hipStream_t)stream>>>(act, (size_t)npts, k, C, out, ldo);
@@ -392,8 +393,10 @@ extern "C" int houv_max_over_k(const float* act, long long npts, int k, int C, f
 extern "C" int houv_layernorm(const float* x, long long rows, int D, const float* a, const float* b, float eps,
                               const float* residual_or_null, float* out, void* stream) {
   using namespace houv;
-  if (rows <= 0 || D < 4 || (D & 3) || !x || !a || !b || !out) {
-    set_error("houv_layernorm: bad argument (D must be a multiple of 4)");
+  if (rows <= 0 || D < 4 || (D & 3) || !x || !a || !b || !out ||
+      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
+        reinterpret_cast<uintptr_t>(residual_or_null) | reinterpret_cast<uintptr_t>(out)) & 15)) {
+    set_error("houv_layernorm: bad argument (D must be a multiple of 4, every pointer 16-byte aligned)");
     return 0;
   }
   layernorm_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, (size_t)rows, D, a, b, eps,

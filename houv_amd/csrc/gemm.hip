@@ -204,7 +204,8 @@ __global__ __launch_bounds__(512, 6) void gemm_f32_kernel(GemmArgs g) {
 //   NPROD = 6:  hi*hi + hi*mid + mid*hi + hi*lo + mid*mid + lo*hi     (dropped terms <= 2^-24 relative: the size of an fp32 rounding)
 //   NPROD = 3:  hi*hi + hi*mid + mid*hi                               (<= 2^-16 relative: 32x finer than TF32)
 // bf16 x bf16 is exact in fp32 and v_mfma_f32_32x32x16_bf16 accumulates in fp32, so NPROD = 6 is an fp32 GEMM to within a small
-// multiple of the fp32 MFMA kernel's own rounding error (tests/test_gpu_dcp_ops.py measures both against fp64).  The matrix pipe
+// multiple of the fp32 MFMA kernel's own rounding error (test_gemm_on_the_bf16_pipe_is_fp32_grade in tests/test_gpu_dcp.py and the
+// gemm tests of tests/test_gpu_dcp_ops.py measure both against fp64 on the same operands).  The matrix pipe
 // runs bf16 at 16x the fp32-input rate (MI355X_MICROARCH.md, Matrix cores), so six products cost 6/16 of the fp32 MFMA time.
 // A tile's elements are split ONCE, while it is staged into LDS (5.5 VALU instructions per element, in the MFMAs' shadow):
 // three bf16 planes per operand, rows of 32 k padded to 80 bytes so that the 16 lanes of a ds_read_b128 group (16 rows) hit 16

@@ -372,16 +372,26 @@ def edgeconv1(xyz, idx, W, scale, shift):
     return out
 
 
+def _aligned16(*tensors):
+    return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
+
+
 def max_over_k(act, k, out, col0):
-    """out[:, col0:col0+C] = max over groups of k consecutive rows of act[npts*k, C]."""
+    """out[:, col0:col0+C] = max over groups of k consecutive rows of act[npts*k, C].  The kernel moves 16 bytes at a time:
+    act and the written view out[:, col0:] must start on 16-byte boundaries."""
     _lib.require_gpu(act); _lib.require_gpu_any(out)
     _want(act, _F32, "act"); _want(out, _F32, "out")
+    if act.dim() != 2 or out.dim() != 2 or k <= 0 or col0 < 0:
+        raise _lib.HouvHipError("max_over_k: expected act[npts*k,C], out[npts, >= col0+C]")
     C = act.shape[1]
-    if act.dim() != 2 or act.shape[0] % k or C % 4 or out.stride(0) % 4 or out.stride(1) != 1 \
+    if act.shape[0] % k or C % 4 or out.stride(0) % 4 or out.stride(1) != 1 \
             or out.shape[0] != act.shape[0] // k or col0 + C > out.shape[1]:
         raise _lib.HouvHipError("max_over_k: expected act[npts*k,C], out[npts, >= col0+C] (C and the row stride multiples of 4)")
     npts = act.shape[0] // k
     view = out[:, col0:col0 + C]
+    if not _aligned16(act, view):
+        raise _lib.HouvHipError("max_over_k: act and out[:, col0:] must start on 16-byte boundaries (col0 a multiple of 4 "
+                                "in a 16-byte aligned buffer)")
     with torch.cuda.device(act.device):
         ok = _lib.load().houv_max_over_k(_lib.ptr(act), npts, int(k), C, ctypes_ptr(view), out.stride(0),
                                          _lib.stream_of(act))
@@ -474,9 +484,13 @@ def layernorm(x, a, b, eps=1e-6, residual=None):
     for t, n in ((x, "x"), (a, "a"), (b, "b"), (residual, "residual")):
         if t is not None:
             _want(t, _F32, n)
+    if x.dim() < 1:
+        raise _lib.HouvHipError("layernorm: expected x[..., D]")
     D = x.shape[-1]
     if a.numel() != D or b.numel() != D or (residual is not None and residual.shape != x.shape):
         raise _lib.HouvHipError("layernorm: a, b must have D elements and residual the shape of x")
+    if not _aligned16(x, a, b, residual):     # rows are read 16 bytes at a time (require_gpu has refused strided views)
+        raise _lib.HouvHipError("layernorm: x, a, b and residual must start on 16-byte boundaries")
     rows = x.numel() // D
     out = torch.empty_like(x)
     with torch.cuda.device(x.device):

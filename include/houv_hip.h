@@ -197,7 +197,8 @@ int houv_knn(const float* xyz, int B, int N, int k, int32_t* idx, void* stream);
 int houv_edgeconv1(const float* xyz, const int32_t* idx, int B, int N, int k, const float* W, const float* scale,
                    const float* shift, float* out, void* stream);
 
-/* dcp.py:287/290/293/296 `x.max(dim=-1)`: out[p*ldo + c] = max_j act[(p*k+j)*C + c], p < npts (C, ldo multiples of 4). */
+/* dcp.py:287/290/293/296 `x.max(dim=-1)`: out[p*ldo + c] = max_j act[(p*k+j)*C + c], p < npts (C, ldo multiples of 4).
+ * act and out (the first written column) must be 16-byte aligned: the kernel moves four floats at a time. */
 int houv_max_over_k(const float* act, long long npts, int k, int C, float* out, int ldo, void* stream);
 
 /* fp32 GEMM on the matrix pipe with fused epilogue (1x1 conv / nn.Linear / attention products):
@@ -221,7 +222,8 @@ int houv_attention_f32(const float* Q, const float* K, const float* V, float* O,
                        int ldq, int ldk, int ldv, int ldo, long long sQ, long long sK, long long sV, long long sO,
                        float scale, void* stream);
 
-/* dcp.py:144-154 LayerNorm: out = a*(x-mean)/(std+eps)+b over the last dim D (torch.std: unbiased) [+ residual]. */
+/* dcp.py:144-154 LayerNorm: out = a*(x-mean)/(std+eps)+b over the last dim D (torch.std: unbiased) [+ residual].
+ * D a multiple of 4; x, a, b, residual and out contiguous and 16-byte aligned. */
 int houv_layernorm(const float* x, long long rows, int D, const float* a, const float* b, float eps,
                    const float* residual_or_null, float* out, void* stream);
 

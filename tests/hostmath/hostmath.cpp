@@ -2,8 +2,35 @@
 // lets the exact code the HIP kernels inline be checked against the oracle without a GPU).
 #include "../../houv_amd/csrc/houv_math.h"
 #include <string.h>
+#include <algorithm>
+#include <cmath>
+#include <utility>
+#include <vector>
 
 extern "C" {
+
+// Brute-force restatement of houv_knn's contract: for every point of xyz[B,N,3] the k smallest (distance, index) pairs in
+// lexicographic order, with the distance of metric_sqdist<0> (houv_common.h): fmaf(dz, dz, fmaf(dy, dy, dx * dx)) in fp32,
+// d = reference - query.  std::fmaf is the correctly rounded fused operation whatever the host; this file is compiled with
+// -ffp-contract=off, so dx * dx stays a rounded product.  idx[B,N,k], dist[B,N,k] (dist may be null).
+void hm_knn_fmaf(const float* xyz, int B, int N, int k, int* idx, float* dist) {
+  std::vector<std::pair<float, int>> row((size_t)N);
+  for (int b = 0; b < B; ++b) {
+    const float* p = xyz + (size_t)b * N * 3;
+    for (int q = 0; q < N; ++q) {
+      const float qx = p[q * 3], qy = p[q * 3 + 1], qz = p[q * 3 + 2];
+      for (int j = 0; j < N; ++j) {
+        const float dx = p[j * 3] - qx, dy = p[j * 3 + 1] - qy, dz = p[j * 3 + 2] - qz;
+        row[j] = std::make_pair(std::fmaf(dz, dz, std::fmaf(dy, dy, dx * dx)), j);
+      }
+      std::partial_sort(row.begin(), row.begin() + k, row.end());     // pair's operator<: distance, then index
+      for (int j = 0; j < k; ++j) {
+        idx[((size_t)b * N + q) * k + j] = row[j].second;
+        if (dist) dist[((size_t)b * N + q) * k + j] = row[j].first;
+      }
+    }
+  }
+}
 
 // params[n,8] -> R[n,9], T[n,3]
 void hm_pose_forward(const float* params, int n, int angle_base, int trans_mode, float* R, float* T) {
