@@ -60,6 +60,9 @@ _SIGNATURES = {
     "houv_emd_forward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _flt, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_emd_workspace_bytes": (ctypes.c_longlong, [_int, _int]),
     "houv_emd_backward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _c_f, _c_f, _c_f, _c_f]),
+    "houv_rri_features": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _c_f]),
+    "houv_gmm_params": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f]),
+    "houv_gmm_register": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _int, _int, _c_f, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

@@ -282,6 +282,59 @@ def emd_backward(xyz1, xyz2, graddist, assignment):
 
 
 # ---------------------------------------------------------------------------------------------------
+# DeepGMR head (houv_rri_features, houv_gmm_params, houv_gmm_register)
+# ---------------------------------------------------------------------------------------------------
+def rri_features(xyz, idx, k, skip=0):
+    """xyz[B,N,3], idx[B,N,L] int32 neighbour lists into the same cloud -> out[B,N,4k]: (|p|, |q_j|, theta_j, phi_j) for the
+    neighbours idx[..., skip:skip+k], channel 4*j + f (get_rri_cluster, registration/models/deepgmr.py:54-95).  2 <= k <= 31."""
+    _lib.require_gpu(xyz, idx)
+    _want(xyz, _F32, "xyz"); _want(idx, _I32, "idx")
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or idx.dim() != 3 or idx.shape[:2] != xyz.shape[:2]:
+        raise _lib.HouvHipError("rri_features: expected xyz[B,N,3], idx[B,N,L]")
+    B, N, _ = xyz.shape
+    out = torch.empty((B, N, 4 * int(k)), dtype=_F32, device=xyz.device)
+    with torch.cuda.device(xyz.device):
+        ok = _lib.load().houv_rri_features(_lib.ptr(xyz), _lib.ptr(idx), B, N, int(k), idx.shape[2], int(skip), _lib.ptr(out),
+                                           _lib.stream_of(xyz))
+    _lib.check(ok, "houv_rri_features")
+    return out
+
+
+def gmm_params(gamma, pts):
+    """gamma[B,N,J] (J <= 32), pts[B,N,3] -> (pi[B,J], mu[B,J,3], sigma[B,J]): deepgmr.py:98-120 with the isotropic covariance kept
+    as its scalar (the reference returns sigma * eye(3))."""
+    _lib.require_gpu(gamma, pts)
+    _want(gamma, _F32, "gamma"); _want(pts, _F32, "pts")
+    if gamma.dim() != 3 or pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[:2] != gamma.shape[:2]:
+        raise _lib.HouvHipError("gmm_params: expected gamma[B,N,J], pts[B,N,3]")
+    B, N, J = gamma.shape
+    pi = torch.empty((B, J), dtype=_F32, device=gamma.device)
+    mu = torch.empty((B, J, 3), dtype=_F32, device=gamma.device)
+    sigma = torch.empty((B, J), dtype=_F32, device=gamma.device)
+    with torch.cuda.device(gamma.device):
+        ok = _lib.load().houv_gmm_params(_lib.ptr(gamma), _lib.ptr(pts), B, N, J, _lib.ptr(pi), _lib.ptr(mu), _lib.ptr(sigma),
+                                         _lib.stream_of(gamma))
+    _lib.check(ok, "houv_gmm_params")
+    return pi, mu, sigma
+
+
+def gmm_register(pi_s, mu_s, mu_t, sigma_t):
+    """pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J] -> T[B,4,4], bottom row (0,0,0,1) (deepgmr.py:123-143)."""
+    _lib.require_gpu(pi_s, mu_s, mu_t, sigma_t)
+    for t, n in ((pi_s, "pi_s"), (mu_s, "mu_s"), (mu_t, "mu_t"), (sigma_t, "sigma_t")):
+        _want(t, _F32, n)
+    if pi_s.dim() != 2 or tuple(mu_s.shape) != tuple(pi_s.shape) + (3,) or mu_t.shape != mu_s.shape or sigma_t.shape != pi_s.shape:
+        raise _lib.HouvHipError("gmm_register: expected pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J]")
+    B, J = pi_s.shape
+    T = torch.empty((B, 4, 4), dtype=_F32, device=pi_s.device)
+    with torch.cuda.device(pi_s.device):
+        ok = _lib.load().houv_gmm_register(_lib.ptr(pi_s), _lib.ptr(mu_s), _lib.ptr(mu_t), _lib.ptr(sigma_t), B, J, _lib.ptr(T),
+                                           _lib.stream_of(pi_s))
+    _lib.check(ok, "houv_gmm_register")
+    return T
+
+
+# ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------
 _registered = False
@@ -311,6 +364,9 @@ def register_torch_ops():
     lib.define("kd_sort(Tensor cloud, int leaf, str rule) -> (Tensor, Tensor)")
     lib.define("emd_forward(Tensor xyz1, Tensor xyz2, float eps, int iters) -> (Tensor, Tensor, Tensor)")
     lib.define("emd_backward(Tensor xyz1, Tensor xyz2, Tensor graddist, Tensor assignment) -> Tensor")
+    lib.define("rri_features(Tensor xyz, Tensor idx, int k, int skip) -> Tensor")
+    lib.define("gmm_params(Tensor gamma, Tensor pts) -> (Tensor, Tensor, Tensor)")
+    lib.define("gmm_register(Tensor pi_s, Tensor mu_s, Tensor mu_t, Tensor sigma_t) -> Tensor")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
     lib.impl("kabsch", kabsch, "CUDA")
@@ -333,6 +389,9 @@ def register_torch_ops():
     lib.impl("kd_sort", _kd_sort, "CUDA")
     lib.impl("emd_forward", emd_forward, "CUDA")
     lib.impl("emd_backward", emd_backward, "CUDA")
+    lib.impl("rri_features", rri_features, "CUDA")
+    lib.impl("gmm_params", gmm_params, "CUDA")
+    lib.impl("gmm_register", gmm_register, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

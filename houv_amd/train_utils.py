@@ -39,6 +39,13 @@ def translation_error(t, t_gt):
     return torch.norm(t - t_gt, dim=1)
 
 
+def rotation_geodesic_error(m1, m2):
+    """Geodesic angle in RADIANS between rotations m1, m2 [B,3,3] (train_utils.py:98-110)."""
+    m = torch.bmm(m1, m2.transpose(1, 2))
+    cos = (m[:, 0, 0] + m[:, 1, 1] + m[:, 2, 2] - 1) / 2
+    return torch.acos(torch.clamp(cos, -1, 1))
+
+
 def rmse_loss(pts, T, T_gt):
     """Mean point displacement between two rigid transforms (train_utils.py:92-95)."""
     pred = pts @ T[:, :3, :3].transpose(1, 2) + T[:, :3, 3].unsqueeze(1)

@@ -310,6 +310,42 @@ long long houv_emd_workspace_bytes(int B, int N);
 int houv_emd_backward(const float* xyz1, const float* xyz2, int B, int N, const float* graddist, const int32_t* assignment,
                       float* gradxyz1, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DeepGMR head (registration/models/deepgmr.py): the two pieces the reference runs on the host.
+ * fp32 data, fixed expression trees, no allocation, no atomics; each returns 0 with houv_last_error() set, launching nothing,
+ * when a check fails. */
+
+/* get_rri_cluster (deepgmr.py:54-95).  xyz[B,N,3]; idx[B,N,idx_ld] neighbour lists into the SAME cloud, of which entries
+ * idx[b,n,idx_skip + j], j = 0..k-1, are used (2 <= k <= 31, idx_skip + k <= idx_ld; an entry outside 0..N-1 is clamped into
+ * that range).  out[B,N,4k], channel 4*j + f, every element written.  For point p with neighbours q_j:
+ *   f=0  rp = |p| = sqrt((x*x + y*y) + z*z)            f=1  rq_j = |q_j|
+ *   f=2  theta_j = acos(clamp(pn.qn_j, -1, 1)),  pn = p/rp, qn_j = q_j/rq_j, dot = (x*x' + y*y') + z*z'
+ *        T_j = q_j - (pn.qn_j) * p        (the cosine multiplies the UNNORMALISED p, as the reference does)
+ *        psi[j,i] = atan2((T_i x T_j).pn, T_i.T_j); a negative value gets float32(2 pi) added; -0 -> 0
+ *   f=3  phi_j = the second smallest of {psi[j,i] : i = 0..k-1} as a multiset, NaNs ranking last (np.sort order); NaN when
+ *        fewer than two are not NaN.
+ * A zero-norm point yields IEEE results (rp = 0, NaN theta/phi where it takes part); nothing is special-cased. */
+int houv_rri_features(const float* xyz, const int32_t* idx, int B, int N, int k, int idx_ld, int idx_skip, float* out,
+                      void* stream);
+
+/* gmm_params (deepgmr.py:98-120).  gamma[B,N,J] responsibilities, pts[B,N,3]; 1 <= J <= 32, N >= 1.
+ *   pi[B,J]    = (sum_n gamma[n,j]) / N
+ *   mu[B,J,3]  = (sum_n gamma[n,j] p_n) / (N pi_j)
+ *   sigma[B,J] = (sum_n gamma[n,j] |p_n - mu_j|^2) / (N pi_j)   one scalar: the reference's isotropic sigma*I, NOT divided by 3
+ * Two passes (mu first, then the deviations about it); one workgroup per cloud; sums run over a fixed tree, so results are
+ * bit-identical from call to call. */
+int houv_gmm_params(const float* gamma, const float* pts, int B, int N, int J, float* pi, float* mu, float* sigma,
+                    void* stream);
+
+/* gmm_register (deepgmr.py:123-143).  pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J] (houv_gmm_params' scalar); J >= 1.
+ *   c_s = sum_j pi_s,j mu_s,j;  c_t = sum_j pi_s,j mu_t,j   (pi_s weights both, as in the reference)
+ *   Ms = sum_j pi_s,j (mu_s,j - c_s)(mu_t,j - c_t)^T / sigma_t,j = U S V^T (singular values sorted, one-sided Jacobi)
+ *   R = V diag(1, 1, det(V U^T)) U^T;  t = c_t - R c_s;  T[B,4,4] = [[R, t], [0, 0, 0, 1]]
+ * The sums and the SVD run in float64 registers on the fp32 inputs (one lane per pair: the arithmetic is free); T is rounded
+ * to fp32 once.  A zero sigma_t propagates inf/NaN into T, as the reference's sigma.inverse() does. */
+int houv_gmm_register(const float* pi_s, const float* mu_s, const float* mu_t, const float* sigma_t, int B, int J, float* T,
+                      void* stream);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
