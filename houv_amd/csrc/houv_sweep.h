@@ -245,6 +245,22 @@ constexpr int pt_base(int k) { return k * BLOCK; }
 // metric m at int16 m, so that the bounds take ONE 8-byte load per query.  `dir_off` = byte offset of the direction's records.
 constexpr int kNnRec = 8;
 
+// r = lanes ? b : a per lane, as ONE v_cndmask on a compare's SGPR pair.  Written out because the compiler turns the nested selects
+// of the walk's unit bookkeeping into two levels of exec-masked branches (s_and_saveexec + s_cbranch_execz + v_mov per level).
+__device__ __forceinline__ unsigned select_mask(unsigned long long lanes, unsigned a, unsigned b) {
+  unsigned r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(lanes));
+  return r;
+}
+
+// Index of the lowest set bit of a 32-bit word, -1 for 0: the bare instruction (the compiler guards __ffs(x) - 1 with a compare and
+// a select for the empty word, which v_ffbl_b32 already answers with -1).
+__device__ __forceinline__ unsigned lowest_bit_or_m1(unsigned x) {
+  unsigned r;
+  asm("v_ffbl_b32_e32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+
 // Minima of the NMET squared distances between one query and the 32 references of ONE sub-tile, gathered per lane, SEPARATELY for the
 // sub-tile's two tracking units (references 0..15 -> ta, 16..31 -> tb).  The lane's sub-tile starts at LDS byte address
 // (xa & ~511); the scan order is rotated per lane by XOR over the 16 slots of a 256-B half -- xa carries (lane & 15) << 4 in bits
@@ -252,13 +268,15 @@ constexpr int kNnRec = 8;
 // clouds 512-B aligned in LDS (solve.hip aligns the dynamic segment); conflict-free as (lane ^ i) % 16 takes 16 distinct slots in
 // every ds_read_b128 lane group.  A min3 takes two references of the SAME half, so the two accumulators cost no instruction more
 // than one.  The reads are software-pipelined: while a batch of four references is being evaluated the next batch is in flight
-// (ping-pong register sets; the trailing prefetch wraps around and is dropped).  Same expression trees as sweep_tile(); the order
-// inside a tracking unit does not matter to a minimum.  ta comes in holding whatever the caller threads through the first unit
-// (its running minima, or +inf); tb is set here.
+// (ping-pong register sets).  The eight batches are written out (no loop): the first min3 of each chain is three-address and takes
+// the caller's running minimum `cb` (first unit) or +inf (second unit) as an operand, so neither accumulator is initialised by a
+// copy; the slot offsets are immediates; and no prefetch runs past the last batch.  Same expression trees as sweep_tile(); the
+// order inside a tracking unit does not matter to a minimum.  ta = min(cb, first unit), tb = min(second unit).
+// NaN: v_min3 returns the minimum of its non-NaN operands, so a NaN distance never enters a chain and a chain that starts at a
+// number (cb is +inf or a distance, never NaN) ends at a number, as in sweep_tile().
 template <int NMET>
-__device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy, float cz, float (&ta)[NMET], float (&tb)[NMET]) {
-#pragma unroll
-  for (int m = 0; m < NMET; ++m) tb[m] = INFINITY;
+__device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy, float cz, const float (&cb)[NMET],
+                                                float (&ta)[NMET], float (&tb)[NMET]) {
   constexpr int kBatch = 4, kHalf = kSub / 2;
   static_assert(kSub == 32 && kHalf == kTrk, "two 256-B tracking units of 16 slots");
   auto fetch = [&](float4 (&r)[kBatch], int i0) {
@@ -270,7 +288,7 @@ __device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy,
       r[u + 1] = make_float4(v1.x, v1.y, v1.z, v1.w);       // second unit
     }
   };
-  auto eval2 = [&](const float4 a, const float4 c, float (&t)[NMET]) {   // two references of one unit
+  auto eval2 = [&](const float4 a, const float4 c, const float (&in)[NMET], float (&t)[NMET]) {   // two references of one unit
     const float ax = a.x - cx, ay = a.y - cy, az = a.z - cz;
     const float bx = c.x - cx, by = c.y - cy, bz = c.z - cz;
     if constexpr (NMET == 4) {
@@ -279,38 +297,47 @@ __device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy,
       const float a1 = __builtin_fmaf(az, az, ayy), b1 = __builtin_fmaf(bz, bz, byy);
       const float a2 = __builtin_fmaf(az, az, axx), b2 = __builtin_fmaf(bz, bz, bxx);
       const float a0 = __builtin_fmaf(az, az, a3), b0 = __builtin_fmaf(bz, bz, b3);
-      t[0] = min3f(t[0], a0, b0);
-      t[1] = min3f(t[1], a1, b1);
-      t[2] = min3f(t[2], a2, b2);
-      t[3] = min3f(t[3], a3, b3);
+      t[0] = min3f(in[0], a0, b0);
+      t[1] = min3f(in[1], a1, b1);
+      t[2] = min3f(in[2], a2, b2);
+      t[3] = min3f(in[3], a3, b3);
     } else {
-      t[0] = min3f(t[0], metric_sqdist<0>(ax, ay, az), metric_sqdist<0>(bx, by, bz));
+      t[0] = min3f(in[0], metric_sqdist<0>(ax, ay, az), metric_sqdist<0>(bx, by, bz));
     }
   };
-  auto eval = [&](float4 (&r)[kBatch]) {
+  float inf[NMET];
+#pragma unroll
+  for (int m = 0; m < NMET; ++m) inf[m] = INFINITY;
+  auto eval = [&](float4 (&r)[kBatch], bool first) {
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) asm volatile("" ::"v"(r[u].x), "v"(r[u].y), "v"(r[u].z), "v"(r[u].w));   // keep b128
     static_assert(kBatch == 4, "a batch = two slots x two units");
-    eval2(r[0], r[2], ta);
-    eval2(r[1], r[3], tb);
+    if (first) {
+      eval2(r[0], r[2], cb, ta);
+      eval2(r[1], r[3], inf, tb);
+    } else {
+      eval2(r[0], r[2], ta, ta);
+      eval2(r[1], r[3], tb, tb);
+    }
   };
   float4 ra[kBatch], rb[kBatch];
   fetch(ra, 0);
-#pragma unroll 1
+#pragma unroll
   for (int i0 = 0; i0 < kHalf; i0 += kBatch) {
     fetch(rb, i0 + kBatch / 2);
-    eval(ra);
-    fetch(ra, i0 + kBatch);
-    eval(rb);
+    eval(ra, i0 == 0);
+    if (i0 + kBatch < kHalf) fetch(ra, i0 + kBatch);
+    eval(rb, false);
   }
 }
 
 // (running minimum, tracking unit) of one query and metric after a sub-tile whose unit minima are ta -- threaded: already
-// min(running, first unit) -- and tb (second unit).  Units are taken in ascending order with strict <, as sweep() takes them.
+// min(running, first unit) -- and tb (second unit).  Units are taken in ascending order with strict <, as sweep() takes them:
+// five instructions, no branch (two compares into SGPR pairs, three selects on them).  A NaN never reaches here (gather_tile_min).
 __device__ __forceinline__ void take_units(float ta, float tb, int unit0, float& cb, int& ct) {
-  const bool la = ta < cb, lb = tb < ta;
-  ct = lb ? unit0 + 1 : (la ? unit0 : ct);
-  cb = lb ? tb : ta;
+  const unsigned long long la = __builtin_amdgcn_ballot_w64(ta < cb), lb = __builtin_amdgcn_ballot_w64(tb < ta);
+  ct = (int)select_mask(lb, select_mask(la, (unsigned)ct, (unsigned)unit0), (unsigned)unit0 + 1u);
+  cb = __uint_as_float(select_mask(lb, __float_as_uint(ta), __float_as_uint(tb)));
 }
 
 // Which sub-tiles each of this lane's queries must visit: the bound per metric is the distance to the point that was the
@@ -418,7 +445,7 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
                                                     buf_t ws, int prev_off, int count, int rot,
                                                     const SortedStage& st, float4* __restrict__ res, float (&best)[Q][NMET],
                                                     int (&btile)[Q][NMET], unsigned long long* __restrict__ stats) {
-  static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "the bin prefix runs on one wave while another resets the block counter");
+  static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "whole waves; thread 64 resets the block counter");
   const int tid = tid_x(), lane = tid & 63;
   unsigned long long un[Q];
   prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
@@ -434,24 +461,27 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
       rnk[k] = atomicAdd(&st.hist[64 - len[k]], 1);        // place inside its bin (any order: results do not depend on it)
     }
   }
+  // barrier S1 -- writers: every thread's bin atomics above; readers: every wave's bin scan below.  It also orders the previous
+  // walk's last block-counter atomics (all before barrier S3 of that sweep) against the counter's reset here.
   __syncthreads();
-  if (tid < 64) {                                           // exclusive prefix over the 65 bins, then clear them for the next sweep
-    const int c = st.hist[tid];
-    const int incl = wave_incl_scan_dpp(c);
-    st.hist[65 + tid] = incl - c;
-    if (tid == 63) st.hist[65 + 64] = incl;                 // bin 64 = empty lists (cannot happen for a valid query; harmless)
-    st.hist[tid] = 0;
-    if (tid == 0) st.hist[64] = 0;
-  } else if (tid == 64) {
-    st.hist[130] = 0;                                       // next block
-  }
-  __syncthreads();
+  // Exclusive prefix over the 65 bins, by EVERY wave for itself (one LDS read per lane + a DPP scan; lane b holds bin b's base and
+  // a query fetches its own with one ds_bpermute): no wave waits for another to publish the bases, which took a barrier of its own.
+  // Bin 64 = empty lists (a query none of whose box tests passes: a NaN coordinate) starts where bin 63 ends.
+  const int bin_c = st.hist[lane];
+  const int bin_incl = wave_incl_scan_dpp(bin_c);
+  const int base64 = __builtin_amdgcn_readlane(bin_incl, 63);
+  if (tid == 64) st.hist[130] = 0;                            // next block
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
     const int q = pt_index<BLOCK>(k);
-    if (q < count) st.order[st.hist[65 + 64 - len[k]] + rnk[k]] = (unsigned short)q;
+    const int bin = 64 - len[k];
+    const int base = __builtin_amdgcn_ds_bpermute((bin & 63) << 2, bin_incl - bin_c);
+    if (q < count) st.order[(bin == 64 ? base64 : base) + rnk[k]] = (unsigned short)q;
   }
+  // barrier S2 -- writers: the order entries and mask slots of every thread, the counter reset; readers: the walk of every wave.
+  // Every wave has also read the bins by now, so one wave clears them for the next sweep (whose atomics come after barrier S3).
   __syncthreads();
+  if (tid < 65) st.hist[tid] = 0;
   const int nblk = (count + 63) >> 6;
   int asked = 0, nsteps = 0;
   for (;;) {
@@ -471,19 +501,23 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
     for (int m = 0; m < NMET; ++m) { cb[m] = INFINITY; ct[m] = 0; }
     asked += __popcll(mm);
     nsteps += cap;
+    // the lane's rotated base address, kept across the steps: a step forms its sub-tile's address with one shift-add
+    const unsigned xbase = (unsigned)(size_t)(lds_f4)refs + (((unsigned)rot & 15u) << 4);
     int t = 0;
 #pragma unroll 1
     for (int s = 0; s < cap; ++s) {
-      t = (mm != 0ull) ? (__ffsll((long long)mm) - 1) : t;
+      // next sub-tile = lowest set bit, found on the 32-bit halves: v_ffbl gives -1 for an empty word, so the lower of
+      // (lo, 32 | hi) as unsigned is the next sub-tile, or -1 for an empty list, which the signed max with t turns into "stay"
+      // (lists ascend: the next sub-tile is above t, and the first one is >= 0 = t).  No 64-bit compare, no select.
+      const unsigned nxt = min(lowest_bit_or_m1((unsigned)mm), lowest_bit_or_m1((unsigned)(mm >> 32)) | 32u);
+      t = max(t, (int)nxt);
       mm &= mm - 1ull;                                                  // 0 stays 0
 #pragma unroll
       for (int h = 0; h < (1 << TS); ++h) {
         const int ts = (t << TS) | h;                                   // sub-tile
-        const unsigned xa = (unsigned)(size_t)(lds_f4)refs + (unsigned)ts * (kSub * 16u) + (((unsigned)rot & 15u) << 4);
-        float ta[NMET], tb[NMET];                                       // the running minima threaded through the first tracking unit
-#pragma unroll
-        for (int m = 0; m < NMET; ++m) ta[m] = cb[m];
-        gather_tile_min<NMET>(xa, qp.x, qp.y, qp.z, ta, tb);
+        const unsigned xa = xbase + (unsigned)ts * (kSub * 16u);
+        float ta[NMET], tb[NMET];                                       // ta: the running minima threaded through the first tracking unit
+        gather_tile_min<NMET>(xa, qp.x, qp.y, qp.z, cb, ta, tb);
 #pragma unroll
         for (int m = 0; m < NMET; ++m) take_units(ta[m], tb[m], 2 * ts, cb[m], ct[m]);
       }
@@ -506,7 +540,9 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
       atomicAdd(&stats[2], 1ull);                                       // one wave-sweep = 64 x Q queries
     }
   }
-  __syncthreads();   // the workgroup's waves share one L1: its global stores above are visible to its loads below
+  // barrier S3 -- writers: the walk's minima (global; the workgroup's waves share one L1) and unit ids (mask slots) of every
+  // wave; readers: the owning lanes below
+  __syncthreads();
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
     const int q = pt_index<BLOCK>(k);

@@ -571,7 +571,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         mz[k] = __builtin_fmaf(sz[k], R[8], __builtin_fmaf(sy[k], R[7], sx[k] * R[6])) + T[2];
         if (ok) sm.mov[i] = make_float4(mx[k], my[k], mz[k], 0.f);
       }
-      __syncthreads();
+      __syncthreads();   // L1 -- writers: every thread's moved points (sm.mov); readers: the walk of sweep A (its queries), sweep B
       // ---- sweep A: moved -> target ----
       bool pruned_now = false;
       if constexpr (PRUNE) {
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_a);
       park_grad_sums<BLOCK, Q, NMET, 1, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
                                                    ws_a);
-      __syncthreads();
+      __syncthreads();   // L2 -- writers: every wave's parked partials of direction A (red_a); readers: wave 0's final_sums
       final_sums<BLOCK, NMET>(sm, 1, true, grad_a);
     }
     unsigned pick_a;
@@ -618,9 +618,9 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       unsigned sel[NMET];
       select_all<BLOCK, Q, NMET>(sm, best, M, a.k_full, a.k_view, hrot, sel);
       park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_b);
-      __syncthreads();
+      __syncthreads();   // L3 -- writers: every wave's parked S of direction B (red_b); readers: wave 0's final_sums
       final_sums<BLOCK, NMET>(sm, 0, true, 0u);
-      __syncthreads();
+      __syncthreads();   // L4 -- writers: wave 0's S of both directions (sm.acc; A's since L2); readers: every thread's picked_direction
       pick_a = picked_direction<NMET>(sm, fresh(a.k_full), fresh(a.k_view));
       const unsigned grad_b = allgrad ? kAllMet : (~pick_a & kAllMet);
       park_grad_sums<BLOCK, Q, NMET, 0, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
@@ -635,12 +635,16 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
           if (miss & 8u) repair_direction_a<BLOCK, Q, 3>(sm, src, N, mpad, a.k_view, hrot, red_a);
         }
       }
-      __syncthreads();
+      __syncthreads();   // L5 -- writers: every wave's parked G / GP of direction B and of the repairs; readers: wave 0's final_sums
       final_sums<BLOCK, NMET>(sm, 0, false, grad_b);
       if (miss) final_sums<BLOCK, NMET>(sm, 1, false, miss);
     }
     pred_a = pick_a;
-    __syncthreads();
+    // No barrier here (there was one): every sm.acc entry the tail reads was written by final_sums, i.e. by threads below
+    // NMET * kAccN <= 64 -- wave 0, the tail's own wave, whose LDS accesses complete in program order; sm.adam's slot of this step
+    // was written before barrier L6 of the previous iteration (or in the prologue).
+    static_assert(NMET * kAccN <= 64, "final_sums runs on the scalar tail's wave");
+    __builtin_amdgcn_wave_barrier();
 
     // ---- per-hypothesis scalar tail: loss, closed-form gradient, Adam, next pose ----
     if (kAdamTid != 0 && tid == kAdamTid && it + 1 < a.n_iters) {   // next iteration's Adam scalars, while thread 0 works below
@@ -724,6 +728,8 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         sm.adam[((step + 1) & 1) * 2 + 1] = nxt.bc2_sqrt;
       }
     }
+    // L6 -- writers: thread 0's next pose (sm.pose) and state, thread kAdamTid's Adam scalars; readers: every thread's move of the
+    // next iteration.  It also ends this iteration's reads of sm.mov (rescans of direction B) before the next move overwrites it.
     __syncthreads();
   }
   if (tid_x() < 24) a.state[(size_t)inst * 24 + tid_x()] = sm.state[tid_x()];   // (the prologue's address is not kept alive)
