@@ -65,7 +65,9 @@ __global__ __launch_bounds__(BLOCK) void fps_kernel(const float* __restrict__ xy
 
 // k nearest points of ref[B,M,3] for every query[B,N,3]: sorted ascending, squared distances out.  The list holds K entries and
 // the first kout <= K are written (rows of kout): the insertion is a stable sort by (distance, index), so the first kout entries
-// of the K-list ARE the kout-list.
+// of the K-list ARE the kout-list.  Stable means: the candidate enters at the first slot it is strictly nearer than, and from
+// there on every entry moves down one slot whether or not it is nearer than the next (re-testing the displaced entry with <
+// would carry it past entries of EQUAL distance and put a higher index in front of a lower one).
 template <int K>
 __global__ __launch_bounds__(256) void knn_cross_kernel(const float* __restrict__ query, const float* __restrict__ ref,
                                                         int N, int M, int kout, float* __restrict__ dist2,
@@ -91,9 +93,10 @@ __global__ __launch_bounds__(256) void knn_cross_kernel(const float* __restrict_
       float d = metric_sqdist<0>(v.x - qx, v.y - qy, v.z - qz);
       if (__any(d < bd[K - 1])) {
         int id = r0 + j;
+        bool lt = false;   // once the candidate is in, every later entry shifts down one slot, equal distances included
 #pragma unroll
         for (int s = 0; s < K; ++s) {
-          const bool lt = d < bd[s];
+          lt = lt || d < bd[s];
           const float td = bd[s]; const int ti = bi[s];
           bd[s] = lt ? d : td;  bi[s] = lt ? id : ti;
           d = lt ? td : d;      id = lt ? ti : id;
@@ -143,9 +146,10 @@ __global__ __launch_bounds__(256) void knn_cross_queued_kernel(const float* __re
       const float2 e = s_q[s][tid];
       float d = s < qn ? e.x : INFINITY;
       int id = __float_as_int(e.y);
+      bool lt = false;
 #pragma unroll
-      for (int t = 0; t < K; ++t) {   // strict <: the earlier index stays first among equal distances
-        const bool lt = d < bd[t];
+      for (int t = 0; t < K; ++t) {   // strict <: the candidate goes behind equal distances (they have lower indices) ...
+        lt = lt || d < bd[t];         // ... and everything behind it shifts: a displaced entry must not jump over its equals
         const float td = bd[t]; const int ti = bi[t];
         bd[t] = lt ? d : td;  bi[t] = lt ? id : ti;
         d = lt ? td : d;      id = lt ? ti : id;

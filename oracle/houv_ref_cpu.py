@@ -334,7 +334,7 @@ def kabsch_svd(src, corr, weights=None):
         H = torch.matmul(sc, cc.transpose(2, 1))
     else:
         H = torch.matmul(sc * weights, cc.transpose(2, 1))
-    reflect = torch.eye(3)
+    reflect = torch.eye(3, dtype=H.dtype)
     reflect[2, 2] = -1
     Rs = []
     for i in range(src.shape[0]):

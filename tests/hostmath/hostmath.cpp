@@ -32,6 +32,28 @@ void hm_knn_fmaf(const float* xyz, int B, int N, int k, int* idx, float* dist) {
   }
 }
 
+// The same for houv_knn_cross: for every point of query[B,N,3] the k smallest (distance, index) pairs of ref[B,M,3] in
+// lexicographic order, same distance expression.  idx[B,N,k], dist[B,N,k] (dist may be null).  k <= M.
+void hm_knn_cross_fmaf(const float* query, const float* ref, int B, int N, int M, int k, int* idx, float* dist) {
+  std::vector<std::pair<float, int>> row((size_t)M);
+  for (int b = 0; b < B; ++b) {
+    const float* qp = query + (size_t)b * N * 3;
+    const float* rp = ref + (size_t)b * M * 3;
+    for (int q = 0; q < N; ++q) {
+      const float qx = qp[q * 3], qy = qp[q * 3 + 1], qz = qp[q * 3 + 2];
+      for (int j = 0; j < M; ++j) {
+        const float dx = rp[j * 3] - qx, dy = rp[j * 3 + 1] - qy, dz = rp[j * 3 + 2] - qz;
+        row[j] = std::make_pair(std::fmaf(dz, dz, std::fmaf(dy, dy, dx * dx)), j);
+      }
+      std::partial_sort(row.begin(), row.begin() + k, row.end());     // pair's operator<: distance, then index
+      for (int j = 0; j < k; ++j) {
+        idx[((size_t)b * N + q) * k + j] = row[j].second;
+        if (dist) dist[((size_t)b * N + q) * k + j] = row[j].first;
+      }
+    }
+  }
+}
+
 // params[n,8] -> R[n,9], T[n,3]
 void hm_pose_forward(const float* params, int n, int angle_base, int trans_mode, float* R, float* T) {
   for (int i = 0; i < n; ++i) {

@@ -1,13 +1,125 @@
-"""Host restatements of the point-op contracts of include/houv_hip.h (houv_ball_query, houv_three_interpolate,
-houv_scatter_points_grad) in NumPy fp32, and of the model_utils_completion helpers in torch, fed index tensors from outside.
+"""Host restatements of the point-op contracts of include/houv_hip.h (houv_furthest_point_sample, houv_knn_cross through
+tests/hostmath, houv_ball_query, houv_three_interpolate, houv_scatter_points_grad) in NumPy fp32, the input families of the
+FPS / k-NN tests, and the model_utils_completion helpers in torch, fed index tensors from outside.
 NumPy evaluates fp32 array expressions operation by operation in fp32 (no contraction, no wider intermediates), so the
 expression trees below are the kernels'."""
+import ctypes
+import functools
 import math
 
 import numpy as np
 import torch
 
 F = np.float32
+
+
+def fps(points, npoint, dtype=F):
+    """points (N,3) -> (npoint,) int32: houv_furthest_point_sample's contract for one cloud.  Every running minimum starts at
+    1e10, the first pick is point 0, then npoint-1 times: d = (dx*dx + dy*dy) + dz*dz to the last pick, md = min(md, d), pick =
+    the arg-max of md with the LOWEST index among equals (np.argmax returns the first).  Once every md is 0 (more picks than
+    distinct points) that is index 0, again and again.  dtype float64 is the yardstick of the CPU test."""
+    p = np.asarray(points, dtype=dtype)
+    md = np.full(len(p), 1e10, dtype)
+    out = [0]
+    for _ in range(1, npoint):
+        q = p[out[-1]]
+        dx, dy, dz = p[:, 0] - q[0], p[:, 1] - q[1], p[:, 2] - q[2]
+        d = (dx * dx + dy * dy) + dz * dz
+        assert d.dtype == dtype
+        md = np.minimum(md, d)
+        out.append(int(np.argmax(md)))
+    return np.array(out, np.int32)
+
+
+def lattice(rng, *shape):
+    """Points on the 1/8 lattice of [0,1)^3 (512 sites): every difference, square and sum of squares is a multiple of 1/64
+    below 3, exact in fp32 whatever the order or contraction."""
+    return (rng.integers(0, 8, shape + (3,)) / 8.0).astype(F)
+
+
+@functools.lru_cache(maxsize=None)
+def fps_cloud(B, N, kind="random"):
+    """(B,N,3) fp32, a different cloud per batch row.  Read-only: shared between tests."""
+    rng = np.random.default_rng(1000 * N + B)
+    x = lattice(rng, B, N) if kind == "lattice" else rng.random((B, N, 3), dtype=F)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def fps_expected(B, N, npoint, kind="random"):
+    x = fps_cloud(B, N, kind)
+    out = np.stack([fps(x[b], npoint) for b in range(B)])
+    out.setflags(write=False)
+    return out
+
+
+def knn_cross(query, ref, k):
+    """(idx[B,N,k] int32, dist2[B,N,k] fp32) of hm_knn_cross_fmaf: per query the k smallest (distance, index) pairs of ref in
+    lexicographic order, distance = fmaf(dz, dz, fmaf(dy, dy, dx*dx)) with d = ref - query (metric_sqdist<0>)."""
+    import hostmath
+    hm = hostmath.load()
+    q = np.ascontiguousarray(query, dtype=F)
+    r = np.ascontiguousarray(ref, dtype=F)
+    B, N, _ = q.shape
+    M = r.shape[1]
+    assert r.shape[0] == B and 1 <= k <= M
+    idx = np.zeros((B, N, k), np.int32)
+    dist = np.zeros((B, N, k), F)
+    fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+    hm.hm_knn_cross_fmaf(q.ctypes.data_as(fp), r.ctypes.data_as(fp), B, N, M, k, idx.ctypes.data_as(ip), dist.ctypes.data_as(fp))
+    return idx, dist
+
+
+KNN_FAMILIES = ("random", "repeat", "identical", "copies", "lattice", "descending")
+
+
+@functools.lru_cache(maxsize=None)
+def knn_inputs(family, B, N, M):
+    """(query[B,N,3], ref[B,M,3]) fp32, read-only.
+    random      uniform, tie-free
+    repeat      the second half of ref repeats the first: every distance is tied once, the lower index comes first
+    identical   ref is M copies of one point: the list must be 0 .. k-1
+    copies      every query is a point of ref (d = 0 heads its list)
+    lattice     both clouds on the 1/8 lattice: exact distances, hundreds of ties per list
+    descending  ref sorted by DEcreasing distance from the origin, queries within 0.05 of it: nearly every reference is a new
+                best, so every reference passes the stale threshold and the queues flush at their maximum rate"""
+    rng = np.random.default_rng([KNN_FAMILIES.index(family), B, N, M])
+    q = rng.random((B, N, 3), dtype=F)
+    r = rng.random((B, M, 3), dtype=F)
+    if family == "repeat":
+        h = M // 2
+        if h:
+            r[:, M - h:] = r[:, :h]
+    elif family == "identical":
+        r[:] = r[:, :1]
+    elif family == "copies":
+        pick = rng.integers(0, M, (B, N))
+        q = np.take_along_axis(r, pick[..., None], axis=1)
+    elif family == "lattice":
+        q, r = lattice(rng, B, N), lattice(rng, B, M)
+    elif family == "descending":
+        order = np.argsort(-(r.astype(np.float64) ** 2).sum(-1), axis=1, kind="stable")
+        r = np.take_along_axis(r, order[..., None], axis=1)
+        q = (q * F(0.05) / F(np.sqrt(3.0))).astype(F)
+    q, r = np.ascontiguousarray(q, dtype=F), np.ascontiguousarray(r, dtype=F)
+    q.setflags(write=False)
+    r.setflags(write=False)
+    return q, r
+
+
+@functools.lru_cache(maxsize=None)
+def knn_expected(family, B, N, M, k):
+    """The k-list as a prefix of ONE host list per input (depth min(M, 32)): a prefix of a lexicographically sorted list is the
+    sorted shorter list."""
+    depth = min(M, 32)
+    if k != depth:
+        idx, dist = knn_expected(family, B, N, M, depth)
+        return idx[..., :k], dist[..., :k]
+    idx, dist = knn_cross(*knn_inputs(family, B, N, M), k)
+    idx.setflags(write=False)
+    dist.setflags(write=False)
+    return idx, dist
 
 
 def ball_query(xyz, center, min_radius, max_radius, nsample):

@@ -74,6 +74,48 @@ def test_adam_matches_torch_f32_and_f64(hm):
             np.testing.assert_allclose(p, tp.detach().numpy(), rtol=tol, atol=tol)
 
 
+@pytest.mark.parametrize("B,N,M,k", [(2, 1, 1, 1), (2, 57, 300, 32), (1, 40, 1025, 17), (1, 9, 33, 33)])
+def test_knn_cross_host_function_equals_float64_sort(hm, B, N, M, k):
+    """hm_knn_cross_fmaf on a tie-free cloud: the same lists, in the same order, as a stable float64 sort of the exact squared
+    distances of the same fp32 differences; the distances within three roundings of them."""
+    import pointops_host as host
+    q, r = host.knn_inputs("random", B, N, M)
+    idx, dist = host.knn_cross(q, r, k)
+    d = r[:, None, :, :] - q[:, :, None, :]
+    assert d.dtype == np.float32
+    exact = (d.astype(np.float64) ** 2).sum(-1)
+    order = np.argsort(exact, axis=-1, kind="stable")[..., :k]
+    srt = np.take_along_axis(exact, order, -1)
+    if M > 1:
+        assert (np.diff(np.sort(exact, -1), axis=-1)[..., :k] > 8 * 2.0 ** -24 * np.sort(exact, -1)[..., 1:k + 1]).all()  # tie-free
+    assert np.array_equal(idx, order)
+    assert (np.abs(dist.astype(np.float64) - srt) <= 3 * 2.0 ** -24 * srt).all()
+
+
+def test_knn_cross_host_function_orders_ties_by_index(hm):
+    import pointops_host as host
+    q, r = host.knn_inputs("identical", 2, 11, 40)
+    idx, dist = host.knn_cross(q, r, 32)
+    assert (idx == np.arange(32)).all() and (dist == dist[..., :1]).all()
+    q, r = host.knn_inputs("repeat", 1, 13, 64)
+    idx, dist = host.knn_cross(q, r, 32)
+    assert (dist[..., 0::2] == dist[..., 1::2]).all() and (idx[..., 1::2] == idx[..., 0::2] + 32).all()
+    q, r = host.knn_inputs("copies", 2, 20, 50)
+    idx, dist = host.knn_cross(q, r, 3)
+    assert (dist[..., 0] == 0).all() and (np.take_along_axis(r, idx[..., :1].astype(np.int64), 1) == q).all()
+    # "descending": nearly every reference enters the 8-list of the references before it (the queued kernels' enqueue test)
+    q, r = host.knn_inputs("descending", 1, 5, 500)
+    d = ((r[:, None].astype(np.float64) - q[:, :, None]) ** 2).sum(-1)[0]
+    assert (np.linalg.norm(q, axis=-1) <= 0.05 + 1e-6).all()
+    enters = [d[n, j] < np.sort(d[n, :j])[7] for n in range(5) for j in range(8, 500)]
+    assert np.mean(enters) > 0.9
+    # a prefix of the 32-list is the shorter list
+    for k in (1, 5, 17):
+        a = host.knn_expected("lattice", 2, 7, 100, k)
+        b = host.knn_cross(*host.knn_inputs("lattice", 2, 7, 100), k)
+        assert np.array_equal(a[0], b[0]) and a[1].tobytes() == np.ascontiguousarray(b[1]).tobytes()
+
+
 def test_svd_and_kabsch(hm, golden):
     rng = np.random.default_rng(9)
     n = 200

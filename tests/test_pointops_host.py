@@ -7,6 +7,33 @@ import torch
 import pointops_host as host
 
 
+@pytest.mark.parametrize("N", [1500, 5000])
+def test_fps_float32_equals_float64_on_the_lattice(N):
+    """On the 1/8 lattice every distance is exact in both types, so the two runs must pick the same points; there are 512
+    sites at most, so the 600 picks run out of distinct points: from then on every running minimum is 0 and the pick is 0."""
+    B, m = 2, 600
+    x = host.fps_cloud(B, N, "lattice")
+    assert np.array_equal(x * 8, np.round(x * 8)) and x.min() >= 0 and x.max() < 1
+    for b in range(B):
+        sites = len(np.unique(x[b], axis=0))
+        assert sites <= 512 < m
+        a = host.fps(x[b], m)
+        assert a.dtype == np.int32 and np.array_equal(a, host.fps(x[b], m, np.float64))
+        assert np.array_equal(a, host.fps_expected(B, N, m, "lattice")[b])
+        assert len(set(a[:sites].tolist())) == sites and (a[sites:] == 0).all()
+        # a tie is broken towards the lowest index: every pick is the first occurrence of its site
+        first = {}
+        for i, p in enumerate(map(tuple, x[b])):
+            first.setdefault(p, i)
+        assert all(first[tuple(x[b, i])] == i for i in a[:sites])
+
+
+def test_fps_starts_at_point_zero_and_from_1e10():
+    x = np.array([[0, 0, 0], [3e5, 0, 0], [1, 0, 0]], np.float32)       # 9e10 > 1e10: the start value caps the first minimum
+    assert host.fps(x, 3).tolist() == [0, 1, 2]
+    assert host.fps(x[:1], 1).tolist() == [0]
+
+
 def test_ball_query_restatement_against_float64_mask():
     """Inputs with margins: coordinates on a 1/64 grid make every squared distance exact in fp32 and in float64, so the hit
     sets of the two agree exactly; the slots then follow from the sets."""
