@@ -63,6 +63,8 @@ _SIGNATURES = {
     "houv_rri_features": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _c_f]),
     "houv_gmm_params": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f]),
     "houv_gmm_register": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _int, _int, _c_f, _c_f]),
+    "houv_idam_simmat": (ctypes.c_int, [_c_f] * 4 + [_int] * 4 + [_c_f] * 15),
+    "houv_edge_diff": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _int, _c_f, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

@@ -335,6 +335,59 @@ def gmm_register(pi_s, mu_s, mu_t, sigma_t):
 
 
 # ---------------------------------------------------------------------------------------------------
+# IDAM head (houv_idam_simmat, houv_edge_diff)
+# ---------------------------------------------------------------------------------------------------
+def idam_simmat(src, tgt, es, et, W1, s1, t1, W2, b2, W3, s3, t3, w4, b4, want_rowmax=True, want_idx=True, want_corr=True,
+                want_scores=False):
+    """One IDAM iteration's similarity stage (registration/models/idam.py:267-320) in one kernel.  src[B,Ms,3], tgt[B,Mt,3],
+    es[B,Ms,E], et[B,Mt,E]; W1[32,2E+4], s1, t1, W2[32,32], b2, W3[32,32], s3, t3, w4 [32], b4 [1] (BatchNorm folded) ->
+    (rowmax[B,Ms,32], corr_idx[B,Ms] int32, corr[B,3,Ms], scores[B,Ms,Mt]), None for an output not asked for."""
+    par = (W1, s1, t1, W2, b2, W3, s3, t3, w4, b4)
+    _lib.require_gpu(src, tgt, es, et, *par)
+    for t in (src, tgt, es, et) + par:
+        _want(t, _F32, "idam_simmat")
+    if src.dim() != 3 or tgt.dim() != 3 or es.dim() != 3 or et.dim() != 3 or src.shape[2] != 3 or tgt.shape[2] != 3 \
+            or es.shape[:2] != src.shape[:2] or et.shape[:2] != tgt.shape[:2] or tgt.shape[0] != src.shape[0] \
+            or et.shape[2] != es.shape[2]:
+        raise _lib.HouvHipError("idam_simmat: expected src[B,Ms,3], tgt[B,Mt,3], es[B,Ms,E], et[B,Mt,E]")
+    B, Ms, E = es.shape
+    Mt = tgt.shape[1]
+    if tuple(W1.shape) != (32, 2 * E + 4) or tuple(W2.shape) != (32, 32) or tuple(W3.shape) != (32, 32) or b4.numel() != 1 \
+            or any(t.numel() != 32 for t in (s1, t1, b2, s3, t3, w4)):
+        raise _lib.HouvHipError("idam_simmat: expected W1[32,2E+4], W2[32,32], W3[32,32], b4[1] and 32-element s1, t1, b2, s3, t3, w4")
+    dev = src.device
+    rowmax = torch.empty((B, Ms, 32), dtype=_F32, device=dev) if want_rowmax else None
+    cidx = torch.empty((B, Ms), dtype=_I32, device=dev) if want_idx else None
+    corr = torch.empty((B, 3, Ms), dtype=_F32, device=dev) if want_corr else None
+    scores = torch.empty((B, Ms, Mt), dtype=_F32, device=dev) if want_scores else None
+    with torch.cuda.device(dev):
+        ok = _lib.load().houv_idam_simmat(_lib.ptr(src), _lib.ptr(tgt), _lib.ptr(es), _lib.ptr(et), B, Ms, Mt, E,
+                                          *[_lib.ptr(t) for t in par], _lib.ptr(rowmax), _lib.ptr(cidx), _lib.ptr(corr),
+                                          _lib.ptr(scores), _lib.stream_of(src))
+    _lib.check(ok, "houv_idam_simmat")
+    return rowmax, cidx, corr, scores
+
+
+def edge_diff(x, idx, k=None, ldo=None):
+    """x[B,N,C], idx[B,N,L] int32 neighbour lists into the same cloud -> out[B*N*k, ldo] with out[(b*N+n)*k + j, :C] =
+    x[b, idx[b,n,j]] - x[b,n] and zeros in columns C..ldo-1 (Propagate, registration/models/idam.py:121-124).  k defaults to
+    L, ldo to C; an index outside 0..N-1 is clamped."""
+    _lib.require_gpu(x, idx)
+    _want(x, _F32, "x"); _want(idx, _I32, "idx")
+    if x.dim() != 3 or idx.dim() != 3 or idx.shape[:2] != x.shape[:2]:
+        raise _lib.HouvHipError("edge_diff: expected x[B,N,C], idx[B,N,L]")
+    B, N, C = x.shape
+    k = idx.shape[2] if k is None else int(k)
+    ldo = C if ldo is None else int(ldo)
+    out = torch.empty((B * N * k, ldo), dtype=_F32, device=x.device)
+    with torch.cuda.device(x.device):
+        ok = _lib.load().houv_edge_diff(_lib.ptr(x), _lib.ptr(idx), B, N, k, C, idx.shape[2], ldo, _lib.ptr(out),
+                                        _lib.stream_of(x))
+    _lib.check(ok, "houv_edge_diff")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------
 _registered = False
@@ -367,6 +420,9 @@ def register_torch_ops():
     lib.define("rri_features(Tensor xyz, Tensor idx, int k, int skip) -> Tensor")
     lib.define("gmm_params(Tensor gamma, Tensor pts) -> (Tensor, Tensor, Tensor)")
     lib.define("gmm_register(Tensor pi_s, Tensor mu_s, Tensor mu_t, Tensor sigma_t) -> Tensor")
+    lib.define("idam_simmat(Tensor src, Tensor tgt, Tensor es, Tensor et, Tensor W1, Tensor s1, Tensor t1, Tensor W2, Tensor b2, "
+               "Tensor W3, Tensor s3, Tensor t3, Tensor w4, Tensor b4) -> (Tensor, Tensor, Tensor, Tensor)")
+    lib.define("edge_diff(Tensor x, Tensor idx, int k, int ldo) -> Tensor")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
     lib.impl("kabsch", kabsch, "CUDA")
@@ -392,6 +448,11 @@ def register_torch_ops():
     lib.impl("rri_features", rri_features, "CUDA")
     lib.impl("gmm_params", gmm_params, "CUDA")
     lib.impl("gmm_register", gmm_register, "CUDA")
+
+    def _simmat(*a):
+        return idam_simmat(*a, want_scores=True)
+    lib.impl("idam_simmat", _simmat, "CUDA")
+    lib.impl("edge_diff", edge_diff, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

@@ -28,6 +28,12 @@ class AverageValueMeter(object):
         self.avg = self.sum / self.count
 
 
+def rt_to_transformation(R, t):
+    """R[B,3,3], t[B,3,1] -> T[B,4,4] with bottom row (0,0,0,1) (train_utils.py:76-79)."""
+    bot_row = torch.tensor([[[0., 0., 0., 1.]]], dtype=R.dtype, device=R.device).repeat(R.shape[0], 1, 1)
+    return torch.cat([torch.cat([R, t], dim=2), bot_row], dim=1)
+
+
 def rotation_error(R, R_gt):
     """Geodesic angle in degrees (train_utils.py:82-85)."""
     cos_theta = (torch.einsum('bij,bij->b', R, R_gt) - 1) / 2

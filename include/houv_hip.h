@@ -346,6 +346,41 @@ int houv_gmm_params(const float* gamma, const float* pts, int B, int N, int J, f
 int houv_gmm_register(const float* pi_s, const float* mu_s, const float* mu_t, const float* sigma_t, int B, int J, float* T,
                       void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * IDAM head (registration/models/idam.py).  fp32 data, fixed expression trees, no allocation, no atomics:
+ * results are bit-identical from call to call.  Each returns 0 with houv_last_error() set, launching nothing, when a check
+ * fails. */
+
+/* One iteration's similarity stage (idam.py:267-320), fused: nothing of size Ms x Mt reaches memory unless `scores` is given.
+ * src[B,Ms,3], tgt[B,Mt,3] points; es[B,Ms,E], et[B,Mt,E] embeddings as rows (16-byte aligned); E a multiple of 4 in 4..128;
+ * Ms, Mt >= 1; any B (B = 0 launches nothing).  Layer parameters, eval-mode BatchNorm folded to per-channel scale/shift by the
+ * caller: W1[32, 2E+4] (columns: E of es, E of et, distance, unit direction x y z), s1[32], t1[32]; W2[32,32], b2[32];
+ * W3[32,32], s3[32], t3[32]; w4[32], b4[1] (a device pointer, like the rest).  Per pair (i, j), all fp32:
+ *   diff = src_i - tgt_j;  d = sqrtf((dx*dx + dy*dy) + dz*dz);  u = diff / (d + 1e-8f)        (d = 0 gives u = 0, not NaN)
+ *   pre_c = (W1[c,:E].es_i + W1[c,E:2E].et_j) + fma(W1[c,2E+3], uz, fma(W1[c,2E+2], uy, fma(W1[c,2E+1], ux, W1[c,2E]*d)))
+ *           the two dot products: sequential fma chains over e ascending, starting from 0
+ *   h1_c = max(fma(s1_c, pre_c, t1_c), 0)
+ *   h2_c = b2_c + sum_k W2[c,k] h1_k                  (an fma chain over k ascending starting from b2_c)
+ *   h3_c = max(fma(s3_c, sum_k W3[c,k] h2_k, t3_c), 0)   (chain from 0)
+ *   score = clamp(b4 + sum_c w4_c h3_c, -20, 20)          (chain over c ascending starting from b4)
+ * Outputs, each may be NULL:
+ *   rowmax[B,Ms,32]   max over j of h2 (the reference takes it before sim_mat_conv2, :289)
+ *   corr_idx[B,Ms]    arg-max over j of score, the LOWEST j among equal scores (rows clamped at +-20 make that a real case)
+ *   corr[B,3,Ms]      tgt[corr_idx], channel-major: houv_kabsch's operand
+ *   scores[B,Ms,Mt]   the clamped scores */
+int houv_idam_simmat(const float* src, const float* tgt, const float* es, const float* et, int B, int Ms, int Mt, int E,
+                     const float* W1, const float* s1, const float* t1, const float* W2, const float* b2, const float* W3,
+                     const float* s3, const float* t3, const float* w4, const float* b4, float* rowmax_or_null,
+                     int32_t* corr_idx_or_null, float* corr_or_null, float* scores_or_null, void* stream);
+
+/* Propagate's edge features (idam.py:121-124): X[B,N,C] rows, idx[B,N,idx_ld] neighbour lists into the SAME cloud, of which the
+ * first k entries of a row are used (k <= idx_ld; an entry outside 0..N-1 is clamped into that range).
+ *   out[((b*N + n)*k + j)*ldo + c] = X[b, idx[b,n,j], c] - X[b,n,c]   for c < C;   0 for C <= c < ldo   (ldo >= C)
+ * Every element of out[B*N*k, ldo] is written.  No alignment is required; 16-byte moves are used when C and ldo are multiples
+ * of 4 and X and out are 16-byte aligned. */
+int houv_edge_diff(const float* X, const int32_t* idx, int B, int N, int k, int C, int idx_ld, int ldo, float* out,
+                   void* stream);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
