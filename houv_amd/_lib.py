@@ -65,6 +65,9 @@ _SIGNATURES = {
     "houv_gmm_register": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _int, _int, _c_f, _c_f]),
     "houv_idam_simmat": (ctypes.c_int, [_c_f] * 4 + [_int] * 4 + [_c_f] * 15),
     "houv_edge_diff": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _int, _c_f, _c_f]),
+    "houv_mlp2_max": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, ctypes.c_longlong, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
+    "houv_mlp2_max_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
+    "houv_pcn_fold": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

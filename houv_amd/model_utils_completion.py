@@ -4,7 +4,8 @@ These are the un-fused, differentiable forms (one Chamfer launch + torch.topk ea
 loop itself never calls them -- it runs inside houv_solve_iterate.
 Below them, the sampling / regularisation helpers of the same file that sit on the mm3d_pn2 point ops
 (edge_preserve_sampling :178-204, get_repulsion_loss :278-297, get_uniform_loss :300-330, knn :346-351, knn_point :354-365,
-symmetric_sample :383-392, three_nn_upsampling :395-402), with the reference's signatures and return tuples."""
+symmetric_sample :383-392, three_nn_upsampling :395-402), with the reference's signatures and return tuples, and the folding
+grids of the completion decoders (gen_grid :223-227, gen_1d_grid :230-233, gen_grid_up :236-249; pure torch, on the CPU)."""
 import math
 
 import torch
@@ -57,6 +58,31 @@ def calc_emd(output, gt, eps=0.005, iterations=50):
     """Mean EMD point distance per cloud: sqrt of the auction's squared distances, averaged (:170-175)."""
     dist, _ = emd()(output, gt, eps, iterations)
     return torch.sqrt(dist).mean(1)
+
+
+def gen_grid(num_grid_point):
+    """[2, n*n]: the flat (x, y) pairs of an n x n mesh over [-0.05, 0.05], VIEWED as two rows (so a row interleaves x and y)."""
+    x = torch.linspace(-0.05, 0.05, steps=num_grid_point)
+    x, y = torch.meshgrid(x, x, indexing="ij")
+    return torch.stack([x, y], dim=-1).view(2, num_grid_point ** 2)
+
+
+def gen_1d_grid(num_grid_point):
+    return torch.linspace(-0.05, 0.05, num_grid_point).view(1, num_grid_point)
+
+
+def gen_grid_up(up_ratio, grid_size=0.2):
+    """[2, up_ratio]: row 0 the x and row 1 the y of a num_x x num_y mesh over [-grid_size, grid_size], num_x the largest divisor
+    of up_ratio that is <= int(sqrt(up_ratio)) + 1."""
+    sqrted = int(math.sqrt(up_ratio)) + 1
+    for i in range(sqrted, 0, -1):
+        if up_ratio % i == 0:
+            num_x, num_y = i, up_ratio // i
+            break
+    grid_x = torch.linspace(-grid_size, grid_size, steps=num_x)
+    grid_y = torch.linspace(-grid_size, grid_size, steps=num_y)
+    x, y = torch.meshgrid(grid_x, grid_y, indexing="ij")
+    return torch.stack([x, y], dim=-1).view(-1, 2).transpose(0, 1).contiguous()
 
 
 def knn_point(pk, point_input, point_output):

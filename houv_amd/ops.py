@@ -388,6 +388,68 @@ def edge_diff(x, idx, k=None, ldo=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# PCN completion network (houv_mlp2_max, houv_pcn_fold)
+# ---------------------------------------------------------------------------------------------------
+PCN_ROW_TILE = 64      # HOUV_PCN_ROW_TILE: points per workgroup of both kernels (a partial tile begins at its multiples)
+
+
+def mlp2_max(x, W1, shift1, W2, b2, want_y=False):
+    """One PointNet block in one kernel (houv_mlp2_max): x[B,N,Cin], W1[H,Cin], shift1[H] (one bias for all clouds) or [B,H]
+    (one row per cloud), W2[Cout,H], b2[Cout] -> (pooled[B,Cout], y[B,N,Cout] or None) with
+    y = W2 . relu(W1 . x + shift1) + b2 and pooled = y.max(1).  (Cin, H, Cout) = (3, 128, 256) or (256, 512, 1024)."""
+    _lib.require_gpu(x, W1, shift1, W2, b2)
+    for t, n in ((x, "x"), (W1, "W1"), (shift1, "shift1"), (W2, "W2"), (b2, "b2")):
+        _want(t, _F32, f"mlp2_max: {n}")
+    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0] \
+            or b2.numel() != W2.shape[0]:
+        raise _lib.HouvHipError(f"mlp2_max: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H], b2[Cout], got {tuple(x.shape)}, "
+                                f"{tuple(W1.shape)}, {tuple(W2.shape)}, {tuple(b2.shape)}")
+    B, N, Cin = x.shape
+    H, Cout = W1.shape[0], W2.shape[0]
+    if tuple(shift1.shape) == (H,):
+        stride = 0
+    elif tuple(shift1.shape) == (B, H):
+        stride = H
+    else:
+        raise _lib.HouvHipError(f"mlp2_max: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    dev = x.device
+    pooled = torch.empty((B, Cout), dtype=_F32, device=dev)
+    y = torch.empty((B, N, Cout), dtype=_F32, device=dev) if want_y else None
+    lib = _lib.load()
+    nbytes = lib.houv_mlp2_max_workspace_bytes(B, N, Cout)
+    ws = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes > 0 else None
+    with torch.cuda.device(dev):
+        ok = lib.houv_mlp2_max(_lib.ptr(x), B, N, Cin, _lib.ptr(W1), H, _lib.ptr(shift1), stride, _lib.ptr(W2), _lib.ptr(b2),
+                               Cout, _lib.ptr(pooled), _lib.ptr(y), _lib.ptr(ws), _lib.stream_of(x))
+    _lib.check(ok, "houv_mlp2_max")
+    return pooled, y
+
+
+def pcn_fold(coarse, cvec, grid, Wgp, W2, b2, W3, b3):
+    """The folding stage of PCN_decoder.forward (registration/models/pcn.py:108-125) in one kernel (houv_pcn_fold):
+    coarse[B,nc,3], cvec[B,512], grid[2,scale], Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3] -> fine[B,nc*scale,3]."""
+    ts = (coarse, cvec, grid, Wgp, W2, b2, W3, b3)
+    _lib.require_gpu(*ts)
+    for t in ts:
+        _want(t, _F32, "pcn_fold")
+    if coarse.dim() != 3 or coarse.shape[2] != 3 or grid.dim() != 2 or grid.shape[0] != 2 \
+            or tuple(cvec.shape) != (coarse.shape[0], 512):
+        raise _lib.HouvHipError(f"pcn_fold: expected coarse[B,nc,3], cvec[B,512], grid[2,scale], got {tuple(coarse.shape)}, "
+                                f"{tuple(cvec.shape)}, {tuple(grid.shape)}")
+    if tuple(Wgp.shape) != (512, 5) or tuple(W2.shape) != (512, 512) or b2.numel() != 512 or tuple(W3.shape) != (3, 512) \
+            or b3.numel() != 3:
+        raise _lib.HouvHipError("pcn_fold: expected Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3]")
+    B, nc, _ = coarse.shape
+    scale = grid.shape[1]
+    fine = torch.empty((B, nc * scale, 3), dtype=_F32, device=coarse.device)
+    with torch.cuda.device(coarse.device):
+        ok = _lib.load().houv_pcn_fold(_lib.ptr(coarse), _lib.ptr(cvec), _lib.ptr(grid), B, nc, scale, _lib.ptr(Wgp), _lib.ptr(W2),
+                                       _lib.ptr(b2), _lib.ptr(W3), _lib.ptr(b3), _lib.ptr(fine), _lib.stream_of(coarse))
+    _lib.check(ok, "houv_pcn_fold")
+    return fine
+
+
+# ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------
 _registered = False
@@ -423,6 +485,8 @@ def register_torch_ops():
     lib.define("idam_simmat(Tensor src, Tensor tgt, Tensor es, Tensor et, Tensor W1, Tensor s1, Tensor t1, Tensor W2, Tensor b2, "
                "Tensor W3, Tensor s3, Tensor t3, Tensor w4, Tensor b4) -> (Tensor, Tensor, Tensor, Tensor)")
     lib.define("edge_diff(Tensor x, Tensor idx, int k, int ldo) -> Tensor")
+    lib.define("mlp2_max(Tensor x, Tensor W1, Tensor shift1, Tensor W2, Tensor b2) -> (Tensor, Tensor)")
+    lib.define("pcn_fold(Tensor coarse, Tensor cvec, Tensor grid, Tensor Wgp, Tensor W2, Tensor b2, Tensor W3, Tensor b3) -> Tensor")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
     lib.impl("kabsch", kabsch, "CUDA")
@@ -453,6 +517,11 @@ def register_torch_ops():
         return idam_simmat(*a, want_scores=True)
     lib.impl("idam_simmat", _simmat, "CUDA")
     lib.impl("edge_diff", edge_diff, "CUDA")
+
+    def _mlp2_max(*a):
+        return mlp2_max(*a, want_y=True)
+    lib.impl("mlp2_max", _mlp2_max, "CUDA")
+    lib.impl("pcn_fold", pcn_fold, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

@@ -381,6 +381,39 @@ int houv_idam_simmat(const float* src, const float* tgt, const float* es, const 
 int houv_edge_diff(const float* X, const int32_t* idx, int B, int N, int k, int C, int idx_ld, int ldo, float* out,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PCN completion network (registration/models/pcn.py).  fp32 in, fp32 out, products on the fp32-input
+ * MFMA (an ordered fma chain over k); no allocation, no atomics, fixed reduction orders: results are bit-identical from call to
+ * call.  Activations are rows [points, channels], weights [out, in] row-major, all densely packed; no pointer needs more than
+ * its natural 4-byte alignment.  Each returns 0 with houv_last_error() set, launching nothing, when a check fails. */
+
+/* Points per workgroup of both kernels: the row tile at whose edges a partial tile begins. */
+#define HOUV_PCN_ROW_TILE 64
+
+/* One PointNet block: a two-layer pointwise MLP with the channel-wise maximum over each cloud's points as its epilogue.
+ *   y[b,n,c]    = W2[c,:] . relu(W1 . x[b,n,:] + shift1[b,:]) + b2[c]
+ *   pooled[b,c] = max over n < N of y[b,n,c]            (a true maximum: all-negative columns pool to a negative value)
+ *                 A NaN in y is stored in y but does NOT reach pooled: the maximum skips NaN (fmaxf), where torch.max
+ *                 propagates it; a column that is NaN in every row pools to -inf.
+ * x[B,N,Cin], W1[H,Cin], W2[Cout,H], b2[Cout]; shift1 is read at shift1 + b * shift1_stride (floats): stride 0 is one bias
+ * shared by all clouds, otherwise stride >= H.  Served (Cin, H, Cout): (3, 128, 256) and (256, 512, 1024); N >= 1; any B (B = 0
+ * launches nothing).  pooled[B,Cout] is always written; y_or_null[B,N,Cout] receives the pre-pool activations when given.  The
+ * hidden [B,N,H] activations never reach memory.  When N spans more than one row tile the per-tile maxima pass through
+ * `workspace` (houv_mlp2_max_workspace_bytes(B, N, Cout) bytes, caller-allocated; may be NULL when that is 0). */
+int houv_mlp2_max(const float* x, int B, int N, int Cin, const float* W1, int H, const float* shift1, long long shift1_stride,
+                  const float* W2, const float* b2, int Cout, float* pooled, float* y_or_null, float* workspace, void* stream);
+long long houv_mlp2_max_workspace_bytes(int B, int N, int Cout);
+
+/* The folding stage of PCN_decoder.forward (pcn.py:108-125).  coarse[B,nc,3], cvec[B,512] (the global feature's share of the
+ * first convolution plus its bias, one vector per cloud), grid[2,scale], Wgp[512,5] (the first convolution's columns for the
+ * two grid and three centre channels), W2[512,512], b2[512], W3[3,512], b3[3]; nc, scale >= 1.  For fine point f = c*scale + s:
+ *   h1 = relu(fma(Wgp[:,4], cz, fma(Wgp[:,3], cy, fma(Wgp[:,2], cx, fma(Wgp[:,1], grid[1,s], Wgp[:,0]*grid[0,s])))) + cvec[b,:])
+ *   h2 = relu(W2 . h1 + b2)
+ *   fine[b,f,:] = (W3 . h2 + b3) + coarse[b,c,:]
+ * fine[B, nc*scale, 3] is the only tensor written. */
+int houv_pcn_fold(const float* coarse, const float* cvec, const float* grid, int B, int nc, int scale, const float* Wgp,
+                  const float* W2, const float* b2, const float* W3, const float* b3, float* fine, void* stream);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
