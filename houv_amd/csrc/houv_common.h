@@ -16,6 +16,10 @@ constexpr int kTrk = 16;      // reference points per arg-min TRACKING unit (hal
 
 // ---- host side ---------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
+// The argument checks every solve entry point shares, in one order (defined in solve.hip; SolveCommon: houv_solve.h).  Returns 0
+// with the error set, 1 when there is nothing to do (P == 0), 2 when `a` may be launched.  Internal: not part of the C ABI.
+struct SolveCommon;
+__attribute__((visibility("hidden"))) int solve_check_args(const char* who, const SolveCommon& a, int use_views);
 inline bool check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

@@ -132,6 +132,84 @@ HOUV_HD inline void adam_step(T& p, T& m, T& v, T g, int step, double lr, double
 }
 
 // ---------------------------------------------------------------------------------------------
+// The per-hypothesis scalar tail of the fused loop (solve.hip, solve_large.hip): what one thread does once both Chamfer
+// directions are summed.  Two halves, so that a kernel can store the last iteration's outputs between them:
+//   solve_tail_loss   loss and closed-form gradient from the 8 x 13 sums
+//   solve_tail_step   Adam step on the 24-double state, pose of the stepped parameters
+// Plain `inline` like the rest of this header, on purpose: with __forceinline__ 17 of the solve_kernel instantiations spilled
+// more registers than with the same text written out in the kernel; the compiler inlines both anyway (no calls remain).
+// ---------------------------------------------------------------------------------------------
+constexpr int kAccN = 13;
+constexpr int kAccStride = 16;   // row stride (floats) of acc and of the reduction scratch in front of it
+
+struct TailLoss {
+  float score, loss;   // the full metric's Chamfer term; 6 * score + the view terms (houv.py:222 / train_utils.py:433)
+  float cd[4][2];      // [metric][dir] mean sqrt distance; 0 for metrics >= NMET
+  float g[8];          // dloss/d(V, a, c, s) * loss_scale
+};
+
+//   acc   [8][acc_stride] floats, slot = metric*2 + dir (dir 0 over the target points, 1 over the moved points), entries
+//         S = sum sqrt(d), G[3] = sum c, GP[9] = sum c p^T (kAccN of them); only slots of metrics < NMET are read
+//   f     pose_forward of the current parameters
+template <int NMET>
+HOUV_HD inline void solve_tail_loss(const float* acc, int acc_stride, const Pose& f, int k_full, int k_view, float loss_scale,
+                                    int trans_mode, TailLoss& r) {
+  float val[NMET];
+  int pick[NMET];
+  float gT[3] = {0.f, 0.f, 0.f}, Mm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  bool bad = false;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) r.cd[m][0] = r.cd[m][1] = 0.f;
+#pragma unroll
+  for (int m = 0; m < NMET; ++m) {
+    const float kk = (float)((m == 0) ? k_full : k_view);
+    r.cd[m][0] = acc[(m * 2 + 0) * acc_stride] / kk;   // over target points   (calc_cd_percent's 1st output)
+    r.cd[m][1] = acc[(m * 2 + 1) * acc_stride] / kk;   // over moved points    (2nd output)
+    // torch.min(cat([first, second])): first wins ties; NaN propagates
+    pick[m] = (r.cd[m][0] <= r.cd[m][1]) ? 0 : 1;
+    val[m] = r.cd[m][pick[m]];
+    if (r.cd[m][0] != r.cd[m][0] || r.cd[m][1] != r.cd[m][1]) { val[m] = NAN; bad = true; }
+    const float w = ((m == 0) ? 6.0f : 1.0f) * loss_scale / kk;
+    const float* ac = acc + (m * 2 + pick[m]) * acc_stride;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) gT[i] += w * ac[1 + i];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Mm[i] += w * ac[4 + i];
+  }
+  r.score = val[0];
+  r.loss = val[0] * 6.0f;                                  // houv.py:222 / train_utils.py:433
+  if constexpr (NMET == 4) r.loss = r.loss + (val[1] + val[2] + val[3]);
+  if (bad) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) gT[i] = NAN;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Mm[i] = NAN;
+  }
+  pose_backward(f, trans_mode, gT, Mm, r.g);
+}
+
+//   state   [24] doubles p | m | v, stepped in place: in fp32 (the doubles then hold float-rounded values) unless f64_params
+//   asc     adam_scalars of this step
+//   next    pose_forward of the stepped parameters (may be the Pose the gradient came from)
+HOUV_HD inline void solve_tail_step(const float g[8], double* state, int f64_params, AdamScalars asc, double beta1, double beta2,
+                                    double eps, int angle_base, int trans_mode, Pose& next) {
+  if (f64_params) {
+    for (int k = 0; k < 8; ++k)
+      adam_step<double>(state[k], state[8 + k], state[16 + k], (double)g[k], asc, beta1, beta2, eps);
+  } else {
+    for (int k = 0; k < 8; ++k) {
+      float pp = (float)state[k], mm = (float)state[8 + k], vv = (float)state[16 + k];
+      adam_step<float>(pp, mm, vv, g[k], asc, beta1, beta2, eps);
+      state[k] = pp; state[8 + k] = mm; state[16 + k] = vv;
+    }
+  }
+  float p[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) p[k] = (float)state[k];
+  pose_forward(p, angle_base, trans_mode, next);
+}
+
+// ---------------------------------------------------------------------------------------------
 // 3x3 SVD by one-sided (Hestenes) Jacobi, register resident.  H = U diag(S) V^T, S sorted
 // descending like torch.svd (model_utils.py:233).
 // ---------------------------------------------------------------------------------------------

@@ -5,8 +5,6 @@
 
 namespace houv {
 
-constexpr int kAccStride = 16;   // row stride (floats) of the per-wave reduction scratch
-
 typedef float houv_f4v __attribute__((ext_vector_type(4)));
 typedef const houv_f4v __attribute__((address_space(3))) * lds_f4;   // LDS pointer usable from a 32-bit byte address
 

@@ -29,25 +29,12 @@
 
 #include "../../include/houv_hip.h"
 #include "houv_common.h"
-#include "houv_sweep.h"
+#include "houv_solve.h"
 
 namespace houv {
 namespace {
 
-struct SolveArgs {
-  const float* src;
-  const float* tgt;
-  int P, N, M, K;
-  double* state;
-  int steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view;
-  double lr, beta1, beta2, eps;
-  float loss_scale;
-  float* out_score;
-  float* out_loss;
-  float* out_R;
-  float* out_T;
-  float* out_grad;
-  float* out_cd;
+struct SolveArgs : SolveCommon {
   short* nn_ws;      // pruned mode, per hypothesis 16 rows of ws_stride int16 (16-byte aligned): rows 0..7 = ws_stride records of
                      // 4 x int16 per direction (kNnRec; direction 0 first) = index of each query's NN per metric in the last
                      // iteration; rows 8..15 = ws_stride float4 of scratch (the balanced walk's minima per query)
@@ -66,13 +53,6 @@ constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS 
 // balanced walk (profiles/r03_ab_refresh.txt): 1 -> 0.697, 2 -> 0.667, 4 -> 0.658, 6 -> 0.657, 8 -> 0.658 us per
 // hypothesis-iteration, identical results; round 2's owner walk, whose steps cost more, preferred 2 (r02_ab_pruned_refresh.txt).
 constexpr int kRefresh = 4;
-constexpr int kAccN = 13;      // sum sqrt(d), G[3], (G p^T)[9]
-
-constexpr int kRedStride = 4 * kAccN;   // per-wave partial sums of one direction: [metric][13]
-constexpr int kHistBins = 256;          // 8-bit radix digits
-constexpr int kHistSets = 3;            // rotating histograms: one barrier per radix pass (see select_smallest)
-constexpr int kPoseFloats = 28;         // sizeof(Pose) / 4 rounded up
-static_assert(sizeof(Pose) <= kPoseFloats * 4 && offsetof(Pose, T) == 36, "sm.pose[0..11] must be R | T");
 
 struct Smem {
   float4* tgt;     // [Mpad]
@@ -142,83 +122,25 @@ __device__ __forceinline__ const float* fresh_lds(const float* p) {
   return (const float*)(lds_f)(size_t)fresh((unsigned)(size_t)(lds_f)p);
 }
 
-__device__ __forceinline__ void store_pose(float* dst, const Pose& f) {
-  const float* src = reinterpret_cast<const float*>(&f);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(Pose) / 4); ++i) dst[i] = src[i];
-}
-__device__ __forceinline__ void load_pose(Pose& f, const float* src) {
-  float* dst = reinterpret_cast<float*>(&f);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(Pose) / 4); ++i) dst[i] = src[i];
-}
-
-// Exact selection of the `ksel` smallest of the BLOCK*Q keys (fp32 bit patterns of non-negative
-// distances; 0xFFFFFFFF marks "not a point").  4-pass 8-bit radix select on LDS histograms.
+// Exact selection of the `ksel` smallest of the BLOCK*Q register-resident keys (fp32 bit patterns of non-negative
+// distances; 0xFFFFFFFF marks "not a point"): houv_solve.h's radix select.
 // Ties at the threshold are taken in (thread, k) order -- torch.topk leaves tie order unspecified.
-//   * ONE barrier per pass: three histograms rotate (`hrot` = the one this pass fills, all-zero on entry).  While pass p
-//     fills set hrot, every thread also clears set hrot+1, whose last readers (pass p-2) are all past the barrier of
-//     pass p-1; after the barrier EVERY wave scans the 256 bins itself (one ds_read_b128 per lane + a DPP prefix sum),
-//     so no broadcast through LDS and no second barrier is needed.
-//   * pass 0 (sign + 7 exponent bits) sees a handful of distinct digits: plain LDS atomics would serialise 64 lanes
-//     on one address, so the wave counts each digit with a ballot and ONE lane adds the count.
 template <int BLOCK, int Q>
 __device__ __forceinline__ void select_smallest(const unsigned (&key)[Q], int ksel, unsigned* hist, int* ctl,
                                                 bool (&sel)[Q], int& hrot) {
   constexpr int NW = BLOCK / 64;
   const int tid = tid_x(), lane = tid & 63, wave = tid >> 6;
-  unsigned prefix = 0u, mask = 0u;
-  int remaining = ksel, neq = 0;
+  RadixState rs{0u, 0u, ksel, 0};
 #pragma unroll
   for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    unsigned* h = hist + hrot * kHistBins;
-    const int nxt = (hrot == kHistSets - 1) ? 0 : hrot + 1;
-    for (int i = tid; i < kHistBins; i += BLOCK) hist[nxt * kHistBins + i] = 0u;
-    if (pass == 0) {
+    unsigned* h = radix_rotate<BLOCK>(hist, hrot, tid);
 #pragma unroll
-      for (int k = 0; k < Q; ++k) {
-        const unsigned digit = key[k] >> 24;
-        unsigned long long todo = __ballot(1);
-        while (todo) {                                           // wave-uniform loop over the distinct digits
-          const int leader = __ffsll((long long)todo) - 1;
-          const unsigned d = (unsigned)__builtin_amdgcn_readlane((int)digit, leader);
-          const unsigned long long m = __ballot(digit == d);
-          if (lane == leader) atomicAdd(&h[d], (unsigned)__popcll(m));
-          todo &= ~m;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < Q; ++k)
-        if ((key[k] & mask) == prefix) atomicAdd(&h[(key[k] >> shift) & 255u], 1u);
-    }
+    for (int k = 0; k < Q; ++k) radix_count(h, key[k], pass, lane, rs);
     __syncthreads();
-    {
-      const uint4 hv = *reinterpret_cast<const uint4*>(h + 4 * lane);
-      const int hh[4] = {(int)hv.x, (int)hv.y, (int)hv.z, (int)hv.w};
-      const int tot = hh[0] + hh[1] + hh[2] + hh[3];
-      int c = wave_incl_scan_dpp(tot) - tot;
-      int fbin = 0, fc = 0, fn = 0;
-      bool found = false;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const bool hit = c < remaining && remaining <= c + hh[b];
-        fbin = hit ? 4 * lane + b : fbin;
-        fc = hit ? c : fc;
-        fn = hit ? hh[b] : fn;
-        found = found || hit;
-        c += hh[b];
-      }
-      const int src_lane = __ffsll((long long)__ballot(found)) - 1;   // exactly one lane holds the bin (1 <= remaining <= total)
-      const int bin = __builtin_amdgcn_readlane(fbin, src_lane);
-      prefix |= (unsigned)bin << shift;
-      mask |= 255u << shift;
-      remaining -= __builtin_amdgcn_readlane(fc, src_lane);
-      neq = __builtin_amdgcn_readlane(fn, src_lane);
-    }
-    hrot = nxt;
+    radix_pick(h, pass, lane, rs);
   }
+  const unsigned prefix = rs.prefix;
+  const int remaining = rs.remaining, neq = rs.neq;
   if (neq == remaining) {
 #pragma unroll
     for (int k = 0; k < Q; ++k) sel[k] = key[k] <= prefix;
@@ -302,12 +224,7 @@ __device__ __forceinline__ void lane_grad_sums(const Smem& sm, const float4* __r
 #pragma unroll
   for (int i = 0; i < kGradN; ++i) g[i] = 0.f;
   float R[9], T[3];
-  if constexpr (DIR == 0) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = sm.pose[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) T[i] = sm.pose[9 + i];
-  }
+  if constexpr (DIR == 0) load_rt(sm.pose, R, T);
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
     int jn;
@@ -430,16 +347,11 @@ __device__ __forceinline__ void repair_direction_a(const Smem& sm, buf_t src, in
                                                    int& hrot, float* red_wave) {
   float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
   float R[9], T[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = sm.pose[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) T[i] = sm.pose[9 + i];
+  load_rt(sm.pose, R, T);
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
     load_src_point<BLOCK>(src, k, N, sx[k], sy[k], sz[k]);
-    mx[k] = __builtin_fmaf(sz[k], R[2], __builtin_fmaf(sy[k], R[1], sx[k] * R[0])) + T[0];
-    my[k] = __builtin_fmaf(sz[k], R[5], __builtin_fmaf(sy[k], R[4], sx[k] * R[3])) + T[1];
-    mz[k] = __builtin_fmaf(sz[k], R[8], __builtin_fmaf(sy[k], R[7], sx[k] * R[6])) + T[2];
+    move_point(R, T, sx[k], sy[k], sz[k], mx[k], my[k], mz[k]);
   }
   float bd[Q];
   int bt[Q];
@@ -485,7 +397,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   for (int j = tid; j < mpad; j += BLOCK) sm.tgt[j] = (j < M) ? make_float4(tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2], 0.f) : pad4;
   for (int j = N + tid; j < npad; j += BLOCK) sm.mov[j] = pad4;
   if (tid < 24) sm.state[tid] = a.state[(size_t)inst * 24 + tid];
-  for (int j = tid; j < kHistBins; j += BLOCK) sm.hist[j] = 0u;   // radix-select histogram set 0 (select_smallest rotates)
+  for (int j = tid; j < kHistBins; j += BLOCK) sm.hist[j] = 0u;   // radix-select histogram set 0 (radix_rotate takes it from there)
   if constexpr (PRUNE) {
     if (tid < 132) sm.st.hist[tid] = 0;                           // list-length bins of the balanced pruned sweep
   }
@@ -555,20 +467,13 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       // ---- move this lane's source points, publish them as references for sweep B ----
       float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
       float R[9], T[3];
-      const float* pose = fresh_lds(sm.pose);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) R[i] = pose[i];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) T[i] = pose[9 + i];
+      load_rt(fresh_lds(sm.pose), R, T);
 #pragma unroll
       for (int k = 0; k < Q; ++k) {
         const int i = pt_index<BLOCK>(k);
         const bool ok = i < N;
         load_src_point<BLOCK>(src, k, N, sx[k], sy[k], sz[k]);
-        // src @ R^T + T (houv.py:102)
-        mx[k] = __builtin_fmaf(sz[k], R[2], __builtin_fmaf(sy[k], R[1], sx[k] * R[0])) + T[0];
-        my[k] = __builtin_fmaf(sz[k], R[5], __builtin_fmaf(sy[k], R[4], sx[k] * R[3])) + T[1];
-        mz[k] = __builtin_fmaf(sz[k], R[8], __builtin_fmaf(sy[k], R[7], sx[k] * R[6])) + T[2];
+        move_point(R, T, sx[k], sy[k], sz[k], mx[k], my[k], mz[k]);
         if (ok) sm.mov[i] = make_float4(mx[k], my[k], mz[k], 0.f);
       }
       __syncthreads();   // L1 -- writers: every thread's moved points (sm.mov); readers: the walk of sweep A (its queries), sweep B
@@ -658,69 +563,15 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       const float loss_scale = fresh(a.loss_scale);
       const double lr = fresh(a.lr), beta1 = fresh(a.beta1), beta2 = fresh(a.beta2), eps = fresh(a.eps);
       const int angle_base = fresh(a.angle_base), trans_mode = fresh(a.trans_mode);
-      float p[8];
       Pose f;
       load_pose(f, sm.pose);        // the forward of the current parameters, kept from the end of the previous tail / the prologue
-      float cd[NMET][2], val[NMET];
-      int pick[NMET];
-      float gT[3] = {0.f, 0.f, 0.f}, Mm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      float loss = 0.f;
-      bool bad = false;
-#pragma unroll
-      for (int m = 0; m < NMET; ++m) {
-        const float kk = (float)((m == 0) ? k_full : k_view);
-        cd[m][0] = sm.acc[(m * 2 + 0) * kAccStride] / kk;   // over target points   (calc_cd_percent's 1st output)
-        cd[m][1] = sm.acc[(m * 2 + 1) * kAccStride] / kk;   // over moved points    (2nd output)
-        // torch.min(cat([first, second])): first wins ties; NaN propagates
-        pick[m] = (cd[m][0] <= cd[m][1]) ? 0 : 1;
-        val[m] = cd[m][pick[m]];
-        if (cd[m][0] != cd[m][0] || cd[m][1] != cd[m][1]) { val[m] = NAN; bad = true; }
-        const float w = ((m == 0) ? 6.0f : 1.0f) * loss_scale / kk;
-        const float* ac = sm.acc + (m * 2 + pick[m]) * kAccStride;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gT[i] += w * ac[1 + i];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Mm[i] += w * ac[4 + i];
-      }
-      loss = val[0] * 6.0f;                                  // houv.py:222 / train_utils.py:433
-      if constexpr (NMET == 4) loss = loss + (val[1] + val[2] + val[3]);
-      if (bad) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gT[i] = NAN;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Mm[i] = NAN;
-      }
-      float g[8];
-      pose_backward(f, trans_mode, gT, Mm, g);
-      if (it == a.n_iters - 1) {
-        // outputs of the LAST forward (houv.py:134-136: the final step is never observed)
-        if (a.out_score) a.out_score[inst] = val[0];
-        if (a.out_loss) a.out_loss[inst] = loss;
-        if (a.out_R)
-          for (int k = 0; k < 9; ++k) a.out_R[(size_t)inst * 9 + k] = f.R[k];
-        if (a.out_T)
-          for (int k = 0; k < 3; ++k) a.out_T[(size_t)inst * 3 + k] = f.T[k];
-        if (a.out_grad)
-          for (int k = 0; k < 8; ++k) a.out_grad[(size_t)inst * 8 + k] = g[k];
-        if (a.out_cd)
-          for (int m = 0; m < 4; ++m)
-            for (int d = 0; d < 2; ++d) a.out_cd[(size_t)inst * 8 + m * 2 + d] = (m < NMET) ? cd[m < NMET ? m : 0][d] : 0.f;
-      }
+      TailLoss r;
+      solve_tail_loss<NMET>(sm.acc, kAccStride, f, k_full, k_view, loss_scale, trans_mode, r);
+      if (it == a.n_iters - 1)
+        store_outputs(a.out_score, a.out_loss, a.out_R, a.out_T, a.out_grad, a.out_cd, inst, f, r);
       const int step = a.steps_done + it + 1;
       const AdamScalars asc{sm.adam[(step & 1) * 2 + 0], sm.adam[(step & 1) * 2 + 1]};
-      if (a.f64_params) {
-        for (int k = 0; k < 8; ++k)
-          adam_step<double>(sm.state[k], sm.state[8 + k], sm.state[16 + k], (double)g[k], asc, beta1, beta2, eps);
-      } else {
-        for (int k = 0; k < 8; ++k) {
-          float pp = (float)sm.state[k], mm = (float)sm.state[8 + k], vv = (float)sm.state[16 + k];
-          adam_step<float>(pp, mm, vv, g[k], asc, beta1, beta2, eps);
-          sm.state[k] = pp; sm.state[8 + k] = mm; sm.state[16 + k] = vv;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) p[k] = (float)sm.state[k];
-      pose_forward(p, angle_base, trans_mode, f);
+      solve_tail_step(r.g, sm.state, a.f64_params, asc, beta1, beta2, eps, angle_base, trans_mode, f);
       store_pose(sm.pose, f);
       if (kAdamTid == 0 && it + 1 < a.n_iters) {                       // single-wave workgroups: no other wave to do it
         const AdamScalars nxt = adam_scalars(step + 1, lr, beta1, beta2);
@@ -805,37 +656,41 @@ extern "C" int houv_solve_variant(int N, int M, int pruned, int* block, int* poi
   return 1;
 }
 
-static int solve_dispatch(const float* src, const float* tgt, int P, int N, int M, int K, double* state, int steps_done,
-                          int n_iters, int angle_base, int trans_mode, int use_views, int f64_params, int k_full,
-                          int k_view, double lr, double beta1, double beta2, double eps, float loss_scale,
-                          float* out_score, float* out_loss, float* out_R, float* out_T, float* out_grad, float* out_cd,
-                          short* nn_ws, int ws_valid, int ws_stride, bool prune, void* stream, const char* who) {
-  using namespace houv;
-  if (P < 0 || N <= 0 || M <= 0 || K <= 0 || n_iters <= 0 || steps_done < 0 || angle_base < 0 || angle_base > 3 ||
-      trans_mode < 0 || trans_mode > 1) {
-    set_error("%s: bad argument P=%d N=%d M=%d K=%d n_iters=%d steps_done=%d base=%d trans_mode=%d", who, P, N, M, K,
-              n_iters, steps_done, angle_base, trans_mode);
+int houv::solve_check_args(const char* who, const SolveCommon& a, int use_views) {
+  const int P = a.P, N = a.N, M = a.M;
+  if (P < 0 || N <= 0 || M <= 0 || a.K <= 0 || a.n_iters <= 0 || a.steps_done < 0 || a.angle_base < 0 || a.angle_base > 3 ||
+      a.trans_mode < 0 || a.trans_mode > 1) {
+    set_error("%s: bad argument P=%d N=%d M=%d K=%d n_iters=%d steps_done=%d base=%d trans_mode=%d", who, P, N, M, a.K,
+              a.n_iters, a.steps_done, a.angle_base, a.trans_mode);
     return 0;
   }
   if (P == 0) return 1;
-  if (!src || !tgt || !state) {
+  if (!a.src || !a.tgt || !a.state) {
     set_error("%s: null pointer", who);
     return 0;
   }
   // topk(k) over a direction with fewer than k points raises in the reference (model_utils_completion.py:91-92)
-  const int kv = use_views ? k_view : 1;
-  if (k_full < 1 || k_full > N || k_full > M || kv < 1 || kv > N || kv > M) {
-    set_error("%s: top-k size out of range (k_full=%d k_view=%d N=%d M=%d)", who, k_full, k_view, N, M);
+  const int kv = use_views ? a.k_view : 1;
+  if (a.k_full < 1 || a.k_full > N || a.k_full > M || kv < 1 || kv > N || kv > M) {
+    set_error("%s: top-k size out of range (k_full=%d k_view=%d N=%d M=%d)", who, a.k_full, a.k_view, N, M);
     return 0;
   }
-  if ((long long)P * K > 0x7fffffffLL) {
+  if ((long long)P * a.K > 0x7fffffffLL) {
     set_error("%s: too many hypotheses", who);
     return 0;
   }
+  return 2;
+}
+
+static int solve_dispatch(const houv::SolveCommon& c, int use_views, short* nn_ws, int ws_valid, int ws_stride, bool prune,
+                          void* stream, const char* who) {
+  using namespace houv;
+  const int ok = solve_check_args(who, c, use_views);
+  if (ok < 2) return ok;
+  const int N = c.N, M = c.M;
   // pred_mode / stats are diagnostics set through houv_debug_set(), never through the environment.
-  SolveArgs a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
-              lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd, nn_ws, ws_valid,
-              ws_stride, g_debug.pred_mode.load(), reinterpret_cast<unsigned long long*>(g_debug.stats.load())};
+  SolveArgs a{c, nn_ws, ws_valid, ws_stride, g_debug.pred_mode.load(),
+              reinterpret_cast<unsigned long long*>(g_debug.stats.load())};
   hipStream_t s = (hipStream_t)stream;
   const int mx = N > M ? N : M;
   int block = 0, q = 0, mode = 0;
@@ -877,9 +732,9 @@ extern "C" int houv_solve_iterate(const float* src, const float* tgt, int P, int
                                   int f64_params, int k_full, int k_view, double lr, double beta1, double beta2,
                                   double eps, float loss_scale, float* out_score, float* out_loss, float* out_R,
                                   float* out_T, float* out_grad, float* out_cd, void* stream) {
-  return solve_dispatch(src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params,
-                        k_full, k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad,
-                        out_cd, nullptr, 0, 0, false, stream, "houv_solve_iterate");
+  const houv::SolveCommon a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
+                            lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd};
+  return solve_dispatch(a, use_views, nullptr, 0, 0, false, stream, "houv_solve_iterate");
 }
 
 extern "C" int houv_solve_iterate_pruned(const float* src, const float* tgt, int P, int N, int M, int K, double* state,
@@ -888,7 +743,7 @@ extern "C" int houv_solve_iterate_pruned(const float* src, const float* tgt, int
                                          double eps, float loss_scale, float* out_score, float* out_loss, float* out_R,
                                          float* out_T, float* out_grad, float* out_cd, int16_t* nn_ws, int ws_valid,
                                          int ws_stride, void* stream) {
-  return solve_dispatch(src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params,
-                        k_full, k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad,
-                        out_cd, (short*)nn_ws, ws_valid, ws_stride, true, stream, "houv_solve_iterate_pruned");
+  const houv::SolveCommon a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
+                            lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd};
+  return solve_dispatch(a, use_views, (short*)nn_ws, ws_valid, ws_stride, true, stream, "houv_solve_iterate_pruned");
 }

@@ -134,7 +134,12 @@ int houv_solve_iterate_pruned(const float* src, const float* tgt, int P, int N, 
  * iterations and pairs).  Same search result as houv_solve_iterate; the sums are grouped differently, so outputs agree to
  * fp32 rounding, not bit for bit.  Deterministic, and chunking along iterations (steps_done) is bit-neutral.
  * Limits: 1 <= N, M <= HOUV_LARGE_MAX_POINTS; with use_views, N == M and k_view == N (the reference's loss_view raises
- * otherwise); 1 <= k_full <= min(N, M).  Returns 0 with houv_last_error() set, launching nothing, when a check fails. */
+ * otherwise); 1 <= k_full <= min(N, M).  Returns 0 with houv_last_error() set, launching nothing, when a check fails.
+ * Order of the checks: the size range and the view rule above first, then the checks houv_solve_iterate makes, in its order:
+ * bad argument, P == 0 (returns 1 at once, before the pointers and k_full are looked at), null pointer, top-k range, too
+ * many hypotheses.  So a call with both a null pointer and a bad k_full reports the null pointer, and a call that breaks the
+ * view rule and also has a bad argument (K <= 0, n_iters <= 0, steps_done < 0, angle_base or trans_mode out of range) reports
+ * the view rule. */
 #define HOUV_LARGE_MAX_POINTS 16384
 int houv_solve_iterate_large(const float* src, const float* tgt, int P, int N, int M, int K,
                              double* state, int steps_done, int n_iters,

@@ -81,6 +81,36 @@ void hm_adam_f64(double* p, double* m, double* v, const double* g, int n, int st
   for (int i = 0; i < n; ++i) houv::adam_step<double>(p[i], m[i], v[i], g[i], step, lr, b1, b2, eps);
 }
 
+// The fused loop's scalar tail (solve_tail_loss<NMET> then solve_tail_step, nmet = 1 or 4) for n hypotheses, the way the kernels call it: the pose of
+// state[0..7], Adam scalars of `step`.  acc[n,8,kAccStride], state[n,24] in/out -> score_loss[n,2], cd[n,8], g[n,8] and the
+// stepped parameters' R[n,9], T[n,3].  Returns 0 for an nmet that is not built.
+int hm_solve_tail(int nmet, int n, const float* acc, double* state, int k_full, int k_view, float loss_scale, int trans_mode,
+                  int angle_base, int f64_params, int step, double lr, double b1, double b2, double eps, float* score_loss,
+                  float* cd, float* g, float* R, float* T) {
+  if (nmet != 1 && nmet != 4) return 0;
+  for (int i = 0; i < n; ++i) {
+    double* st = state + 24 * i;
+    float p[8];
+    for (int k = 0; k < 8; ++k) p[k] = (float)st[k];
+    houv::Pose f;
+    houv::pose_forward(p, angle_base, trans_mode, f);
+    houv::TailLoss r;
+    const float* a = acc + (size_t)i * 8 * houv::kAccStride;
+    if (nmet == 1)
+      houv::solve_tail_loss<1>(a, houv::kAccStride, f, k_full, k_view, loss_scale, trans_mode, r);
+    else
+      houv::solve_tail_loss<4>(a, houv::kAccStride, f, k_full, k_view, loss_scale, trans_mode, r);
+    houv::solve_tail_step(r.g, st, f64_params, houv::adam_scalars(step, lr, b1, b2), b1, b2, eps, angle_base, trans_mode, f);
+    score_loss[2 * i] = r.score;
+    score_loss[2 * i + 1] = r.loss;
+    memcpy(cd + 8 * i, r.cd, sizeof(r.cd));
+    memcpy(g + 8 * i, r.g, sizeof(r.g));
+    memcpy(R + 9 * i, f.R, sizeof(f.R));
+    memcpy(T + 3 * i, f.T, sizeof(f.T));
+  }
+  return 1;
+}
+
 void hm_svd3x3_f32(const float* H, int n, float* U, float* S, float* V) {
   for (int i = 0; i < n; ++i) houv::svd3x3<float>(H + 9 * i, U + 9 * i, S + 3 * i, V + 9 * i);
 }
