@@ -37,6 +37,7 @@ _SIGNATURES = {
                                                  _c_f, _c_f, _c_f, _int, _int, _c_f]),
     "houv_solve_variant": (ctypes.c_int, [_int, _int, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int)]),
+    "houv_solve_lds_bytes": (ctypes.c_longlong, [_int, _int, _int]),
     "houv_kd_sort": (ctypes.c_int, [_c_f, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_icp_refine": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _flt, _int, _flt, _flt, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_knn": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _c_f]),

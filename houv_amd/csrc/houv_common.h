@@ -32,7 +32,7 @@ inline bool check_launch(const char* what) {
 // Diagnostic switches (houv_debug_set; tests, A/B scripts and bench.py only -- never the environment).  Results are proven
 // independent of every switch except the two that select the matrix-pipe kernels (gemm_split, attn_split).
 //   "solve_predict"   0 normal; 1 always predict direction B (every A-win takes the repair path); 2 rescan everything
-//   "solve_stats"     device address of 6 uint64 counters the fused loop adds to (0 = off): see SolveArgs::stats
+//   "solve_stats"     device address of 8 uint64 counters the fused loop adds to (0 = off): see SolveArgs::stats
 //   "knn_split"       houv_knn: 1 references split over the four waves of a workgroup (same lists), 0 the single-scan kernel
 //   "attn_split"      houv_attention_f32: 1 bf16 matrix pipe with three-part splits (full tiles), 0 fp32-input MFMA kernel
 //   "gemm_split"      houv_gemm_f32: 0 fp32-input MFMA, 6 / 3 = bf16 part products per fp32 product (gemm.hip, gemm_split_kernel)

@@ -210,6 +210,71 @@ HOUV_HD inline void solve_tail_step(const float g[8], double* state, int f64_par
 }
 
 // ---------------------------------------------------------------------------------------------
+// Term masks of the pruned solve (solve.hip, PRUNE != 0): which of the eight Chamfer terms cd[metric][dir] an iteration has
+// to compute.  solve_tail_loss takes min(cd[m][0], cd[m][1]) per metric; the loser's value only decides that it lost.  If an
+// earlier iteration (the ANCHOR) computed all eight terms and the moved cloud has not travelled far since, the loser is known
+// without computing it.
+//
+// Proof sketch.  Let every moved point R p + T lie within d of its anchor position.  A nearest-neighbour distance -- full or
+// in an axis-dropped projection (a projection is 1-Lipschitz), moved -> target or target -> moved -- changes by at most d; so
+// does each of the k smallest of them in sorted order, hence their mean: every term is 1-Lipschitz in the displacement.  With
+//   d <= ||R - R_anchor||_F * radius + |T - T_anchor|      (radius = max |p| over the source cloud; Frobenius >= spectral norm)
+// a term Y with  cd_X + 2 d < cd_Y  at the anchor still satisfies cd_X < cd_Y now: Y loses and need not be computed.
+//
+// Margin (what fp32 adds to the real-number argument; u = 2^-24 = 6.0e-8):
+//   * move_point: 4 roundings per coordinate of magnitudes <= radius + |T_i|, so a computed moved point is within
+//     sqrt(3) * 4 u * (radius + |T|) = 4.2e-7 * (radius + |T|) of R p + T; at the anchor and now together
+//     4.2e-7 * (2 radius + |T| + |T_anchor|) on d, which enters the inequality doubled: kTermMoveErr = 1e-6 times that sum;
+//   * a computed term against the real one on the same computed points: squared distance 3 subtractions, products and two or
+//     three FMAs (<= 6 u relative), sqrt (half of that + u = 4 u), a sum of up to 4096 non-negative terms in any grouping
+//     (<= 4095 u), the division by k (u): <= 4100 u = 2.5e-4 relative.  It acts on cd_X and cd_Y at the anchor and again now:
+//     3 * 2.5e-4 < kTermRel = 1e-3 of (cd_X + cd_Y) covers both to first order with a quarter to spare;
+//   * d's own evaluation (21 subtractions / products / sums, two sqrt, radius from one more sqrt: < 30 u relative) is covered
+//     by applying kTermRel to 2 d as well;
+//   * kTermAbs = 1e-6 absorbs flushed subnormals and makes an exact tie keep both terms.
+// A term is dropped only on the STRICT inequality, so never both of a metric; any NaN or Inf among the operands (a term, a
+// pose entry, the radius: 0 * Inf included) makes the comparisons false and keeps both terms (the margin takes |cd|, so an
+// infinity of either sign turns both sides of its comparisons into Inf or NaN).
+//   anchor  [kTermAnchorFloats] = cd[metric * 2 + dir] (8) | R (9) | T (3) of the anchor iteration
+//   R, T    the pose the coming iteration moves the cloud with
+// Returns the terms needed: bit m = the term of metric m over the target points (dir 0), bit 4 + m = over the moved points
+// (dir 1).  Branch-free on purpose (selects on values): the kernels inline it into their scalar tail.
+// ---------------------------------------------------------------------------------------------
+constexpr int kTermAnchorFloats = 20;
+constexpr float kTermRel = 1e-3f;
+constexpr float kTermAbs = 1e-6f;
+constexpr float kTermMoveErr = 1e-6f;
+
+template <int NMET>
+HOUV_HD inline unsigned term_masks(const float* anchor, const float* R, const float* T, float radius) {
+  float fr = 0.f, ft = 0.f, tn = 0.f, ta = 0.f;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const float d = R[i] - anchor[8 + i];
+    fr += d * d;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float d = T[i] - anchor[17 + i];
+    ft += d * d;
+    tn += T[i] * T[i];
+    ta += anchor[17 + i] * anchor[17 + i];
+  }
+  const float delta2 = 2.0f * (sqrtf(fr) * radius + sqrtf(ft));
+  const float abs_margin = kTermAbs + kTermMoveErr * (2.0f * radius + sqrtf(tn) + sqrtf(ta));
+  unsigned need = ((1u << NMET) - 1u) * 0x11u;
+#pragma unroll
+  for (int m = 0; m < NMET; ++m) {
+    const float c0 = anchor[2 * m], c1 = anchor[2 * m + 1];
+    const float slack = delta2 + kTermRel * (fabsf(c0) + fabsf(c1) + delta2) + abs_margin;
+    const unsigned drop1 = (c0 + slack < c1) ? (0x10u << m) : 0u;   // at most one of the two holds (slack > 0)
+    const unsigned drop0 = (c1 + slack < c0) ? (1u << m) : 0u;
+    need &= ~(drop0 | drop1);
+  }
+  return need;
+}
+
+// ---------------------------------------------------------------------------------------------
 // 3x3 SVD by one-sided (Hestenes) Jacobi, register resident.  H = U diag(S) V^T, S sorted
 // descending like torch.svd (model_utils.py:233).
 // ---------------------------------------------------------------------------------------------

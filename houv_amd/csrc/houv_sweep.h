@@ -340,10 +340,13 @@ __device__ __forceinline__ void take_units(float ta, float tb, int unit0, float&
 
 // Which sub-tiles each of this lane's queries must visit: the bound per metric is the distance to the point that was the
 // query's nearest neighbour in the previous iteration (`prev`, attained), the test a point-to-box distance per metric.
+// `need` (workgroup-uniform; term_masks, houv_math.h): bit m clear = this direction's term of metric m provably loses the min
+// and is not computed: its bound is -1, so no box passes on its account and the lists shrink.
 template <int BLOCK, int Q, int NMET>
 __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                             const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                            buf_t ws, int prev_off, int count, unsigned long long (&un)[Q]) {
+                                            buf_t ws, int prev_off, int count, unsigned need,
+                                            unsigned long long (&un)[Q]) {
   float ub[Q][NMET];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
@@ -366,7 +369,8 @@ __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, con
       { const float4 r = refs[w1 >> 16]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
     }
 #pragma unroll
-    for (int m = 0; m < NMET; ++m) ub[k][m] = ok ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;   // box distances are rounded: stay conservative
+    for (int m = 0; m < NMET; ++m)   // box distances are rounded: stay conservative
+      ub[k][m] = (ok && ((need >> m) & 1u)) ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;
   }
   unsigned alo[Q], ahi[Q];
 #pragma unroll
@@ -436,17 +440,18 @@ __device__ __forceinline__ unsigned& w_slot(float4* cloud, int q) { return reint
 // after the walk, the tracking-unit ids (8 bits each: <= 256 units of 16 references) of its minima; .w of whi[q] the high half.
 // TS = 1 (clouds of 2049..4096 points): the masks are over 64 SUPER-tiles of two sub-tiles each (`boxes`, `ntile` count
 // super-tiles); a visit evaluates both sub-tiles in ascending order, the minima carry tracking-unit ids (0..255) for the rescans.
+// `need`: see prune_masks; (best, btile) of a metric whose bit is clear are garbage (the minimum over another metrics' lists).
 template <int BLOCK, int Q, int NMET, int TS = 0>
 __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                                     const float4* __restrict__ qarr, float4* wlo, float4* whi,
                                                     const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                                    buf_t ws, int prev_off, int count, int rot,
+                                                    buf_t ws, int prev_off, int count, unsigned need, int rot,
                                                     const SortedStage& st, float4* __restrict__ res, float (&best)[Q][NMET],
                                                     int (&btile)[Q][NMET], unsigned long long* __restrict__ stats) {
   static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "whole waves; thread 64 resets the block counter");
   const int tid = tid_x(), lane = tid & 63;
   unsigned long long un[Q];
-  prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, un);
+  prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, need, un);
   int len[Q], rnk[Q];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {

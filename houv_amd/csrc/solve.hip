@@ -45,7 +45,8 @@ struct SolveArgs : SolveCommon {
   unsigned long long* stats;   // houv_debug_set("solve_stats", device pointer): [0] sub-tile visits the lanes of the pruned sweeps
                                // asked for, [1] sub-tile steps their waves executed, [2] pruned wave-sweeps, [3] brute wave-sweeps,
                                // [4] shader clocks (s_memtime) and [5] 100-MHz ticks (s_memrealtime) summed over the workgroups'
-                               // loops: [4]/[5] x 100 MHz = the clock the chip sustained under THIS kernel's load
+                               // loops: [4]/[5] x 100 MHz = the clock the chip sustained under THIS kernel's load; pruned kernels:
+                               // [6] Chamfer terms computed and [7] terms possible (2 x metrics), per workgroup-iteration
 };
 
 constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS reads (recover_nn)
@@ -67,7 +68,12 @@ struct Smem {
   float4* tbox;    // [2*64] lo/hi boxes of the target's 32-point sub-tiles   (pruned mode only)
   float4* mbox;    // [2*64] same for the moved cloud, rebuilt every iteration
   SortedStage st;  // staging of the balanced pruned sweep (pruned mode only)
+  float* anchor;   // [kAnchorFloats] term masks (pruned mode only): the anchor iteration's eight cd and pose | the source radius
 };
+// The term masks themselves travel in ctl[0]: bits 0..3 = terms needed over the target points (direction B), 4..7 = over the
+// moved points (direction A); written by thread 0 in the scalar tail (and the prologue), read by every thread after barrier L6.
+constexpr int kAnchorFloats = kTermAnchorFloats + 4;   // [kTermAnchorFloats] = radius of the source cloud about the origin
+
 
 // prune: 0 brute force, 2 pruned (balanced walk: + staging for block * q queries)
 // PRUNE == 3: the balanced walk over 64-point SUPER-tiles (pairs of sub-tiles) for clouds of 2049..4096 points: the clouds are
@@ -81,7 +87,7 @@ __host__ __device__ inline size_t smem_bytes(int N, int M, int block, int prune,
   const int nw = block / 64;
   const size_t nq = (size_t)block * q;
   return (size_t)(npad + mpad) * 16 + 28 * 8 + kPoseFloats * 4 + 8 * kAccStride * 4 + (size_t)2 * nw * kRedStride * 4 +
-         kHistSets * kHistBins * 4 + (8 + nw) * 4 + 64 + (prune ? 2 * 128 * 16 + nq * 2 + 132 * 4 : 0);
+         kHistSets * kHistBins * 4 + (8 + nw) * 4 + 64 + (prune ? 2 * 128 * 16 + nq * 2 + 132 * 4 + kAnchorFloats * 4 : 0);
 }
 
 // nq = BLOCK * Q for the balanced pruned sweep (PRUNE != 0), 0 otherwise; pu = pad_unit(PRUNE)
@@ -107,6 +113,7 @@ __device__ inline Smem carve(unsigned char* base, int N, int M, int block, int n
   // balanced pruned sweep only (the pointers are never used otherwise)
   s.st.hist = reinterpret_cast<int*>(s.mbox + 128);
   s.st.order = reinterpret_cast<unsigned short*>(s.st.hist + 132);
+  s.anchor = reinterpret_cast<float*>(s.st.order + nq);   // nq is even: 4-byte aligned
   return s;
 }
 
@@ -182,7 +189,7 @@ __device__ __forceinline__ void park(float v, float* dst) {
 // selections of one direction: bit k of bits[m] = query k of this lane takes part in metric m's mean
 template <int BLOCK, int Q, int NMET>
 __device__ __forceinline__ void select_all(const Smem& sm, const float (&best)[Q][NMET], int count, int k_full, int k_view,
-                                           int& hrot, unsigned (&bits)[NMET]) {
+                                           unsigned need, int& hrot, unsigned (&bits)[NMET]) {
   bool valid[Q], sel[Q];
   unsigned key[Q];
 #pragma unroll
@@ -194,7 +201,8 @@ __device__ __forceinline__ void select_all(const Smem& sm, const float (&best)[Q
       key[k] = valid[k] ? __float_as_uint(best[k][m]) : 0xFFFFFFFFu;
       sel[k] = valid[k];
     }
-    if (ksel < count) select_smallest<BLOCK, Q>(key, ksel, sm.hist, sm.ctl, sel, hrot);
+    // an unneeded term's selection is never used; `need` is workgroup-uniform, so the barriers inside stay matched
+    if (ksel < count && ((need >> m) & 1u)) select_smallest<BLOCK, Q>(key, ksel, sm.hist, sm.ctl, sel, hrot);
     unsigned b = 0u;
 #pragma unroll
     for (int k = 0; k < Q; ++k) b |= sel[k] ? (1u << k) : 0u;
@@ -260,10 +268,12 @@ __device__ __forceinline__ void lane_grad_sums(const Smem& sm, const float4* __r
 
 // S of every metric of one direction: per-lane sums -> wave totals parked in red[dir][wave][m*13]
 template <int BLOCK, int Q, int NMET>
-__device__ __forceinline__ void park_sqrt_sums(const float (&best)[Q][NMET], const unsigned (&selbits)[NMET], float* red_wave) {
+__device__ __forceinline__ void park_sqrt_sums(const float (&best)[Q][NMET], const unsigned (&selbits)[NMET], unsigned need,
+                                               float* red_wave) {
   float bd[Q];
 #pragma unroll
   for (int m = 0; m < NMET; ++m) {
+    if (!((need >> m) & 1u)) continue;   // final_sums writes +inf for an unneeded term
 #pragma unroll
     for (int k = 0; k < Q; ++k) bd[k] = best[k][m];
     park(lane_sqrt_sum<Q>(bd, selbits[m]), red_wave + m * kAccN);
@@ -298,9 +308,11 @@ __device__ __forceinline__ void park_grad_sums(const Smem& sm, const float4* __r
 #undef HOUV_GRAD
 }
 
-// cross-wave sums (wave order) of the parked partials into sm.acc[(metric*2+dir)][..]; call after a barrier
+// cross-wave sums (wave order) of the parked partials into sm.acc[(metric*2+dir)][..]; call after a barrier.
+// S of a term that was not computed (bit clear in `need`) is +inf: picked_direction and solve_tail_loss then take the other
+// direction, which the term mask proved to be the winner, with the bits the brute-force kernel gives it.
 template <int BLOCK, int NMET>
-__device__ __forceinline__ void final_sums(const Smem& sm, int dir, bool want_s, unsigned grad_mask) {
+__device__ __forceinline__ void final_sums(const Smem& sm, int dir, bool want_s, unsigned grad_mask, unsigned need) {
   constexpr int NW = BLOCK / 64;
   const int tid = tid_x();
   if (tid < NMET * kAccN) {
@@ -310,6 +322,7 @@ __device__ __forceinline__ void final_sums(const Smem& sm, int dir, bool want_s,
       float a = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) a += r[w * kRedStride];
+      if (i == 0 && !((need >> m) & 1u)) a = INFINITY;
       sm.acc[(m * 2 + dir) * kAccStride + i] = a;
     }
   }
@@ -438,7 +451,30 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     sm.adam[(step & 1) * 2 + 0] = asc.step_size;
     sm.adam[(step & 1) * 2 + 1] = asc.bc2_sqrt;
   }
+  if constexpr (PRUNE) {
+    // term masks: the first iteration of a launch computes every term (the anchor does not travel through `state`); the
+    // radius of the source cloud about the origin is one max-reduce (a NaN or Inf coordinate gives +inf: no term is ever dropped)
+    float r2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+      float x, y, z;
+      load_src_point<BLOCK>(src, k, N, x, y, z);
+      const float v = __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x));
+      r2 = (v <= r2) ? r2 : ((v < INFINITY) ? v : INFINITY);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) r2 = fmaxf(r2, __shfl_xor(r2, o, 64));
+    if ((tid & 63) == 0) sm.red[tid >> 6] = r2;
+    if (tid == 0) sm.ctl[0] = (int)(((1u << NMET) - 1u) * 0x11u);
+  }
   __syncthreads();
+  if constexpr (PRUNE) {
+    if (tid == 0) {   // sm.red is next written after barrier L1, which this thread reaches after these reads
+      float r2 = 0.f;
+      for (int w = 0; w < BLOCK / 64; ++w) r2 = fmaxf(r2, sm.red[w]);
+      sm.anchor[kTermAnchorFloats] = sqrtf(r2) * 1.000001f;   // rounded up
+    }
+  }
 
   unsigned long long clk0 = 0ull, rt0 = 0ull;   // two stamps per LAUNCH (not per iteration), only when the counters are on
   if (a.stats) {
@@ -458,11 +494,18 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   float* red_b = sm.red + ((size_t)0 * NW + (tid >> 6)) * kRedStride;
 #pragma unroll 1
   for (int it = 0; it < a.n_iters; ++it) {
-    float best[Q][NMET];
-    int btile[Q][NMET];
     if (a.pred_mode == 1) pred_a = 0u;
     const bool allgrad = a.pred_mode == 2 || ((PRUNE != 0) && (((a.steps_done + it) % kRefresh) == 0 || (a.ws_valid == 0 && it == 0)));
-    const unsigned grad_a = allgrad ? kAllMet : pred_a;
+    // Term masks (term_masks, houv_math.h): a term that provably loses its metric's min is not computed -- no search, no
+    // selection, no sums, no rescans; its remembered NNs stay as they are (an older neighbour is still an attained bound).  The
+    // proof also settles the prediction: where B's term is dropped A is the winner, and the other way round.  Workgroup-uniform.
+    unsigned need_a = kAllMet, need_b = kAllMet;
+    if constexpr (PRUNE != 0) {
+      const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(sm.ctl[0]);
+      need_b = w & kAllMet;
+      need_a = (w >> 4) & kAllMet;
+    }
+    const unsigned grad_a = allgrad ? kAllMet : ((pred_a | ~need_b) & need_a);
     {
       // ---- move this lane's source points, publish them as references for sweep B ----
       float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
@@ -479,26 +522,30 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       __syncthreads();   // L1 -- writers: every thread's moved points (sm.mov); readers: the walk of sweep A (its queries), sweep B
       // ---- sweep A: moved -> target ----
       bool pruned_now = false;
+      float best[Q][NMET];
+      int btile[Q][NMET];
       if constexpr (PRUNE) {
         tile_boxes<BLOCK, Q, TS>(mx, my, mz, N, npad / kPad, sm.mbox);   // read by sweep B after the next barriers
         pruned_now = (a.ws_valid != 0) || (it > 0);
       }
-      if (pruned_now) {
-        if constexpr (PRUNE != 0)
-          pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
-                                              rot, sm.st, ws_res, best, btile, a.stats);
-      } else {
-        sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
-        if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
+      if (need_a != 0u) {   // none of A's terms needed: no walk, no selection, no sums (the move and the boxes above are for sweep B)
+        if (pruned_now) {
+          if constexpr (PRUNE != 0)
+            pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
+                                                need_a, rot, sm.st, ws_res, best, btile, a.stats);
+        } else {
+          sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
+          if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
+        }
+        // ---- epilogue A: selection, S of every needed metric, G/GP of the predicted-A metrics; one barrier ----
+        unsigned sel[NMET];
+        select_all<BLOCK, Q, NMET>(sm, best, N, a.k_full, a.k_view, need_a, hrot, sel);
+        park_sqrt_sums<BLOCK, Q, NMET>(best, sel, need_a, red_a);
+        park_grad_sums<BLOCK, Q, NMET, 1, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
+                                                     ws_a);
       }
-      // ---- epilogue A: selection, S of every metric, G/GP of the predicted-A metrics; one barrier ----
-      unsigned sel[NMET];
-      select_all<BLOCK, Q, NMET>(sm, best, N, a.k_full, a.k_view, hrot, sel);
-      park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_a);
-      park_grad_sums<BLOCK, Q, NMET, 1, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
-                                                   ws_a);
       __syncthreads();   // L2 -- writers: every wave's parked partials of direction A (red_a); readers: wave 0's final_sums
-      final_sums<BLOCK, NMET>(sm, 1, true, grad_a);
+      final_sums<BLOCK, NMET>(sm, 1, true, grad_a, need_a);
     }
     unsigned pick_a;
     {
@@ -511,25 +558,38 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         tx[k] = v.x; ty[k] = v.y; tz[k] = v.z;
       }
       const bool pruned_now = (PRUNE != 0) && ((a.ws_valid != 0) || (it > 0));
-      if (pruned_now) {
-        if constexpr (PRUNE != 0)
-          pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
-                                              rot, sm.st, ws_res, best, btile, a.stats);
-      } else {
-        sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
-        if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
+      // The barriers between B's S and B's G / GP: once with B's sweep state alive around them, once without (need_b is
+      // workgroup-uniform, so all waves meet in the same pair).  Written twice so that B's minima are scoped to the branch that
+      // computes them: as values merged after a skipped sweep they were carried around the iteration loop, in spilled VGPRs.
+      auto pick_winners = [&]() {
+        __syncthreads();   // L3 -- writers: every wave's parked S of direction B (red_b); readers: wave 0's final_sums
+        final_sums<BLOCK, NMET>(sm, 0, true, 0u, need_b);
+        __syncthreads();   // L4 -- writers: wave 0's S of both directions (sm.acc; A's since L2); readers: every thread's picked_direction
+        pick_a = picked_direction<NMET>(sm, fresh(a.k_full), fresh(a.k_view));
+        return (allgrad ? kAllMet : (~pick_a & kAllMet)) & need_b;   // an unneeded term's +inf never wins
+      };
+      unsigned grad_b = 0u;
+      if (need_b != 0u) {
+        float best[Q][NMET];
+        int btile[Q][NMET];
+        if (pruned_now) {
+          if constexpr (PRUNE != 0)
+            pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
+                                                need_b, rot, sm.st, ws_res, best, btile, a.stats);
+        } else {
+          sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
+          if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
+        }
+        // ---- epilogue B: selection and S first; then the winners are known to every thread ----
+        unsigned sel[NMET];
+        select_all<BLOCK, Q, NMET>(sm, best, M, a.k_full, a.k_view, need_b, hrot, sel);
+        park_sqrt_sums<BLOCK, Q, NMET>(best, sel, need_b, red_b);
+        grad_b = pick_winners();
+        park_grad_sums<BLOCK, Q, NMET, 0, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
+                                                     ws_b);
+      } else {   // none of B's terms needed: every metric's winner is A, proven
+        pick_winners();
       }
-      // ---- epilogue B: selection and S first; then the winners are known to every thread ----
-      unsigned sel[NMET];
-      select_all<BLOCK, Q, NMET>(sm, best, M, a.k_full, a.k_view, hrot, sel);
-      park_sqrt_sums<BLOCK, Q, NMET>(best, sel, red_b);
-      __syncthreads();   // L3 -- writers: every wave's parked S of direction B (red_b); readers: wave 0's final_sums
-      final_sums<BLOCK, NMET>(sm, 0, true, 0u);
-      __syncthreads();   // L4 -- writers: wave 0's S of both directions (sm.acc; A's since L2); readers: every thread's picked_direction
-      pick_a = picked_direction<NMET>(sm, fresh(a.k_full), fresh(a.k_view));
-      const unsigned grad_b = allgrad ? kAllMet : (~pick_a & kAllMet);
-      park_grad_sums<BLOCK, Q, NMET, 0, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
-                                                   ws_b);
       // ---- repair: won by A, but A's rescans were skipped ----
       const unsigned miss = pick_a & ~grad_a & kAllMet;
       if (miss) {
@@ -541,8 +601,8 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         }
       }
       __syncthreads();   // L5 -- writers: every wave's parked G / GP of direction B and of the repairs; readers: wave 0's final_sums
-      final_sums<BLOCK, NMET>(sm, 0, false, grad_b);
-      if (miss) final_sums<BLOCK, NMET>(sm, 1, false, miss);
+      final_sums<BLOCK, NMET>(sm, 0, false, grad_b, kAllMet);
+      if (miss) final_sums<BLOCK, NMET>(sm, 1, false, miss, kAllMet);
     }
     pred_a = pick_a;
     // No barrier here (there was one): every sm.acc entry the tail reads was written by final_sums, i.e. by threads below
@@ -569,18 +629,44 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       solve_tail_loss<NMET>(sm.acc, kAccStride, f, k_full, k_view, loss_scale, trans_mode, r);
       if (it == a.n_iters - 1)
         store_outputs(a.out_score, a.out_loss, a.out_R, a.out_T, a.out_grad, a.out_cd, inst, f, r);
+      if constexpr (PRUNE != 0) {
+        if ((need_a & need_b) == kAllMet) {   // every term was computed: this iteration is the anchor of the coming term masks
+#pragma unroll
+          for (int m = 0; m < 4; ++m) {
+            sm.anchor[2 * m] = r.cd[m][0];
+            sm.anchor[2 * m + 1] = r.cd[m][1];
+          }
+#pragma unroll
+          for (int i = 0; i < 9; ++i) sm.anchor[8 + i] = f.R[i];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) sm.anchor[17 + i] = f.T[i];
+        }
+      }
       const int step = a.steps_done + it + 1;
       const AdamScalars asc{sm.adam[(step & 1) * 2 + 0], sm.adam[(step & 1) * 2 + 1]};
       solve_tail_step(r.g, sm.state, a.f64_params, asc, beta1, beta2, eps, angle_base, trans_mode, f);
       store_pose(sm.pose, f);
+      if constexpr (PRUNE != 0) {
+        // The coming iteration's term masks.  Every term is computed -- and so the anchor renewed -- on every kRefresh-th
+        // iteration, on the first iteration of a launch (prologue) and on the last one (its eight cd are outputs), and always
+        // under pred_mode 2; in between, term_masks drops what the anchor and the pose just stepped to prove unnecessary.
+        unsigned next = kAllMet | (kAllMet << 4);
+        const bool all_next = fresh(a.pred_mode) == 2 || ((a.steps_done + it + 1) % kRefresh) == 0 || it + 2 >= a.n_iters;
+        if (!all_next) next = term_masks<NMET>(sm.anchor, f.R, f.T, sm.anchor[kTermAnchorFloats]);
+        sm.ctl[0] = (int)next;
+        if (a.stats) {
+          atomicAdd(&a.stats[6], (unsigned long long)(__popc(need_a) + __popc(need_b)));
+          atomicAdd(&a.stats[7], (unsigned long long)(2 * NMET));
+        }
+      }
       if (kAdamTid == 0 && it + 1 < a.n_iters) {                       // single-wave workgroups: no other wave to do it
         const AdamScalars nxt = adam_scalars(step + 1, lr, beta1, beta2);
         sm.adam[((step + 1) & 1) * 2 + 0] = nxt.step_size;
         sm.adam[((step + 1) & 1) * 2 + 1] = nxt.bc2_sqrt;
       }
     }
-    // L6 -- writers: thread 0's next pose (sm.pose) and state, thread kAdamTid's Adam scalars; readers: every thread's move of the
-    // next iteration.  It also ends this iteration's reads of sm.mov (rescans of direction B) before the next move overwrites it.
+    // L6 -- writers: thread 0's next pose (sm.pose), term masks (sm.ctl[0]) and state, thread kAdamTid's Adam scalars; readers:
+    // every thread's move of the next iteration.  It also ends this iteration's reads of sm.mov (rescans of direction B) before the next move overwrites it.
     __syncthreads();
   }
   if (tid_x() < 24) a.state[(size_t)inst * 24 + tid_x()] = sm.state[tid_x()];   // (the prologue's address is not kept alive)
@@ -654,6 +740,13 @@ extern "C" int houv_solve_variant(int N, int M, int pruned, int* block, int* poi
   constexpr int kPrunedMinPoints = 257;
   if (prune_mode) *prune_mode = (!pruned || mx < kPrunedMinPoints) ? 0 : (mx > 2048) ? 3 : 2;
   return 1;
+}
+
+extern "C" long long houv_solve_lds_bytes(int N, int M, int pruned) {
+  using namespace houv;
+  int block = 0, q = 0, mode = 0;
+  if (!houv_solve_variant(N, M, pruned, &block, &q, &mode)) return -1;
+  return (long long)smem_bytes(N, M, block, mode, q);
 }
 
 int houv::solve_check_args(const char* who, const SolveCommon& a, int use_views) {

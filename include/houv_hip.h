@@ -158,6 +158,11 @@ int houv_solve_iterate_large(const float* src, const float* tgt, int P, int N, i
  * the test-suite can prove that every variant is compared with the CPU oracle. */
 int houv_solve_variant(int N, int M, int pruned, int* block, int* points_per_lane, int* prune_mode);
 
+/* Bytes of LDS one workgroup of that variant reserves (host-only query, no GPU work), -1 with houv_last_error() set when no
+ * variant serves the size.  Exported so that the test-suite can assert that two workgroups of the 512-thread pruned kernel
+ * still share a CU's 160 KiB. */
+long long houv_solve_lds_bytes(int N, int M, int pruned);
+
 /* The point order houv_solve_iterate_pruned wants, on the device: every cloud reordered so that consecutive runs of `leaf` points
  * are the leaves of a balanced k-d tree -- bit for bit the permutation of houv_amd.solver.kd_sort (torch) on the same device.
  * Lexicographic (x, y, z) start; then, level by level, every range of more than one tile (tiles = ceil(len / leaf)) is cut at
