@@ -307,6 +307,9 @@ long long houv_scatter_points_workspace_bytes(int B, int N, int M);
  * N <= 4096 runs entirely in LDS and takes no workspace; 4097..16384 needs a caller-allocated device workspace of
  * houv_emd_workspace_bytes(B, N) bytes (no alignment beyond 4 bytes; its contents on entry are ignored).  Nothing is allocated
  * in here.  Results are deterministic: bit-identical from call to call and to the sequential restatement of this contract.
+ * Non-finite coordinates are the caller's error but stay in range: a bidder whose values are all NaN bids for object 0 with a
+ * NaN increment (whose bits outrank every finite key, so it takes object 0 and keeps it), its dist is NaN, every assignment
+ * stays in [0, N), and the other clouds of the batch are not affected.
  * Returns 0 with houv_last_error() set, launching nothing, when a check fails. */
 int houv_emd_forward(const float* xyz1, const float* xyz2, int B, int N, int M, float eps, int iters, float* dist,
                      int32_t* assignment, int32_t* iters_run_or_null, void* workspace_or_null, void* stream);
