@@ -275,6 +275,120 @@ HOUV_HD inline unsigned term_masks(const float* anchor, const float* R, const fl
 }
 
 // ---------------------------------------------------------------------------------------------
+// Term masks with PER-TERM records (the rule solve.hip runs; term_masks above is the shared-anchor rule it grew out of and
+// the reference it is tested against).  Every term Z carries its own record: its value cd_Z when it was last computed and
+// the pose (R_Z, T_Z) it was computed at.  For metric m with terms X and Y, Y is dropped for the coming iteration iff
+//   cd_X + d_X + d_Y + margin < cd_Y        (strictly),
+// d_Z bounding how far any moved point now is from where it was at Z's record:
+//   d_Z = rho(R, R_Z) * radius + |T - T_Z|.
+// Proof: every term is 1-Lipschitz in the displacement (see above), so now  X <= cd_X + d_X  and  Y >= cd_Y - d_Y.
+//
+// rho bounds the spectral norm ||R - R_Z||_2.  For two exact rotations A, B:  A - B = (A B^T - I) B, and a rotation Q = A B^T
+// by the angle t has the eigenvalues 1, e^{+-it}, so Q - I (normal) has the singular values 0, 2 sin(t/2), 2 sin(t/2):
+//   ||A - B||_2 = 2 sin(t/2),  ||A - B||_F = sqrt(2) * 2 sin(t/2),  hence  ||A - B||_2 = ||A - B||_F / sqrt(2)  exactly.
+// The poses are fp32 outputs of pose_forward, not exact rotations.  Write R = A S (polar decomposition, A orthogonal, S
+// symmetric positive semi-definite with eigenvalues s_i): ||R - A||_F^2 = sum (s_i - 1)^2 <= sum (s_i^2 - 1)^2 =
+// ||R^T R - I||_F^2 =: defect(R)^2, because |s - 1| <= |s - 1| (s + 1).  With B the polar factor of R_Z and
+// e = defect(R) + defect(R_Z):
+//   ||R - R_Z||_2 <= ||A - B||_2 + e = ||A - B||_F / sqrt(2) + e <= (||R - R_Z||_F + e) / sqrt(2) + e
+//                 <  ||R - R_Z||_F / sqrt(2) + 2 e.
+// That needs A B^T to be a ROTATION (for a reflection Q, Q - I has a singular value 2 and the identity fails).  A B^T is
+// improper only when exactly one of A, B is; then ||A - B||_2 = 2, so ||R - R_Z||_F >= 2 - e.  The sqrt(2) form is therefore
+// taken only where e <= kTermDefectMax = 1e-3 AND ||R - R_Z||_F^2 <= 2 (rotations up to 60 degrees apart; an optimiser step
+// is far below), and only where it is the smaller bound; everywhere else rho is the Frobenius norm itself, as in term_masks.
+// Each defect is evaluated here in fp32: 9 entries of R^T R - I, each three products of entries <= 1 summed and 1 taken off,
+// <= 4 u of error, so <= 12 u = 7.2e-7 on the norm; kTermDefectErr = 1e-6 is added to each.
+//
+// Margin, re-derived for two records (u = 2^-24):
+//   * move_point: a computed moved point is within 4.2e-7 * (radius + |T_pose|) of R p + T at any pose.  The computed X moved
+//     by d_X plus that error at X's record pose and now; the same for Y: 4.2e-7 * (4 radius + |T_X| + |T_Y| + 2 |T|)
+//     = 8.4e-7 * (2 radius + |T| + (|T_X| + |T_Y|) / 2) <= kTermMoveErr = 1e-6 times that sum (with both records at one
+//     pose this is term_masks' margin);
+//   * a computed term is within 2.5e-4 relative of the real one on the same computed points, at its record and now:
+//     (1 + e)(cd_X / (1 - e) + d_X) < (1 - e)(cd_Y / (1 + e) - d_Y) follows from the rule to first order with
+//     3 * 2.5e-4 < kTermRel of (cd_X + cd_Y + d_X + d_Y), which also covers the evaluation of d_X, d_Y themselves (< 60 u);
+//   * kTermAbs absorbs flushed subnormals and makes an exact tie keep both terms.
+// Strict inequality only, so never both terms of a metric; any NaN or Inf operand (a cd, an entry of any of the poses the
+// metric uses, the radius; 0 * Inf included) makes the comparisons false: both terms kept.  Branch-free (selects on values).
+//
+// At most ONE term per metric is older than the last iteration in the kernels, so the records are passed as
+//   cd     [8] = cd[metric * 2 + dir] when last computed
+//   fresh  R (9) | T (3): the record pose of every term that is not stale (the pose of the iteration that just ended)
+//   stale  R (9) | T (3) per metric, entry i of metric m at stale[(m * 12 + i) * stride]
+//   stale_bits  bit m / bit 4 + m set: the record pose of the term (metric m, dir 0 / 1) is stale's; clear: fresh
+//   R, T   the pose the coming iteration moves the cloud with
+// Returns the terms needed, as term_masks does.
+// ---------------------------------------------------------------------------------------------
+constexpr float kTermDefectMax = 1e-3f;
+constexpr float kTermDefectErr = 1e-6f;
+
+// ||M^T M - I||_F + kTermDefectErr of a row-major 3x3
+HOUV_HD inline float term_rot_defect(const float* M) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j) {
+      const float g = M[i] * M[j] + M[3 + i] * M[3 + j] + M[6 + i] * M[6 + j] - ((i == j) ? 1.0f : 0.0f);
+      s += ((i == j) ? 1.0f : 2.0f) * g * g;
+    }
+  return sqrtf(s) + kTermDefectErr;
+}
+
+// d_Z and |T_Z| of one record pose; def_now = term_rot_defect(R)
+HOUV_HD inline void term_travel(const float* Rz, const float* Tz, const float* R, const float* T, float def_now, float radius,
+                                float& d, float& tz) {
+  float fr = 0.f, ft = 0.f, ta = 0.f;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const float e = R[i] - Rz[i];
+    fr += e * e;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float e = T[i] - Tz[i];
+    ft += e * e;
+    ta += Tz[i] * Tz[i];
+  }
+  const float fro = sqrtf(fr), defect = def_now + term_rot_defect(Rz);
+  const float tight = fro * 0.70710683f + 2.0f * defect;   // the constant is 1 / sqrt(2) rounded UP
+  const bool ok = (fr <= 2.0f) & (defect <= kTermDefectMax) & (tight < fro);   // any NaN: false, and fro is NaN too
+  d = (ok ? tight : fro) * radius + sqrtf(ft);
+  tz = sqrtf(ta);
+}
+
+template <int NMET>
+HOUV_HD inline unsigned term_anchor_masks(const float* cd, const float* fresh, const float* stale, int stride,
+                                          unsigned stale_bits, const float* R, const float* T, float radius_in) {
+  const float radius = fabsf(radius_in);   // a negative infinity must not turn the slack negative
+  const float def_now = term_rot_defect(R);
+  const float tn = sqrtf(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
+  float d_f, t_f;
+  term_travel(fresh, fresh + 9, R, T, def_now, radius, d_f, t_f);
+  unsigned need = ((1u << NMET) - 1u) * 0x11u;
+#pragma unroll
+  for (int m = 0; m < NMET; ++m) {
+    float Rs[9], Ts[3], d_s, t_s;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Rs[i] = stale[(m * 12 + i) * stride];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Ts[i] = stale[(m * 12 + 9 + i) * stride];
+    term_travel(Rs, Ts, R, T, def_now, radius, d_s, t_s);
+    const bool s0 = (stale_bits >> m) & 1u, s1 = (stale_bits >> (4 + m)) & 1u;
+    const float d0 = s0 ? d_s : d_f, d1 = s1 ? d_s : d_f;
+    const float t0 = s0 ? t_s : t_f, t1 = s1 ? t_s : t_f;
+    const float c0 = cd[2 * m], c1 = cd[2 * m + 1];
+    const float dd = d0 + d1;
+    const float slack = dd + kTermRel * (fabsf(c0) + fabsf(c1) + dd) + kTermAbs +
+                        kTermMoveErr * (2.0f * radius + tn + 0.5f * (t0 + t1));
+    const unsigned drop1 = (c0 + slack < c1) ? (0x10u << m) : 0u;   // at most one of the two holds (slack > 0)
+    const unsigned drop0 = (c1 + slack < c0) ? (1u << m) : 0u;
+    need &= ~(drop0 | drop1);
+  }
+  return need;
+}
+
+// ---------------------------------------------------------------------------------------------
 // 3x3 SVD by one-sided (Hestenes) Jacobi, register resident.  H = U diag(S) V^T, S sorted
 // descending like torch.svd (model_utils.py:233).
 // ---------------------------------------------------------------------------------------------

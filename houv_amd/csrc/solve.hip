@@ -50,10 +50,16 @@ struct SolveArgs : SolveCommon {
 };
 
 constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS reads (recover_nn)
-// pruned mode: every kRefresh-th iteration rescans everything and so refreshes every remembered NN.  Same-device A/B of the
+// pruned mode: every kRefresh-th iteration rescans every computed term and so refreshes its remembered NNs.  Same-device A/B of the
 // balanced walk (profiles/r03_ab_refresh.txt): 1 -> 0.697, 2 -> 0.667, 4 -> 0.658, 6 -> 0.657, 8 -> 0.658 us per
 // hypothesis-iteration, identical results; round 2's owner walk, whose steps cost more, preferred 2 (r02_ab_pruned_refresh.txt).
 constexpr int kRefresh = 4;
+// term masks: a term is dropped for at most this many iterations in a row, then computed once; 0: no limit (a launch's last
+// iteration computes every term anyway).  A limit bounds how stale a dropped term's remembered NNs get -- its visit lists are long
+// for the one iteration of its return -- but every forced return is a term computed for nothing.  Same-device A/B at 2,048 points
+// (profiles/r11_ab_term_anchors.txt): no limit 0.3510 / 0.3520, 12 -> 0.3520 / 0.3526, 6 -> 0.3544 / 0.3550 us per
+// hypothesis-iteration, identical results.
+constexpr int kTermMaxAge = 0;
 
 struct Smem {
   float4* tgt;     // [Mpad]
@@ -65,14 +71,21 @@ struct Smem {
   float* red;      // [2 dirs][NW][kRedStride]
   unsigned* hist;  // [kHistSets][256]
   int* ctl;        // [8 + NW]
-  float4* tbox;    // [2*64] lo/hi boxes of the target's 32-point sub-tiles   (pruned mode only)
+  float4* tbox;    // [2*64] lo/hi boxes of the target's 32-point sub-tiles   (pruned mode only); x, y, z only: the .w lanes
+                   // [0..47] hold the term masks' stale record poses (R | T per metric), see kStalePose
   float4* mbox;    // [2*64] same for the moved cloud, rebuilt every iteration
   SortedStage st;  // staging of the balanced pruned sweep (pruned mode only)
-  float* anchor;   // [kAnchorFloats] term masks (pruned mode only): the anchor iteration's eight cd and pose | the source radius
+  float* anchor;   // [kAnchorFloats] term masks (pruned mode only): the eight cd records, [kTermAges] the drop ages, | the source radius
 };
 // The term masks themselves travel in ctl[0]: bits 0..3 = terms needed over the target points (direction B), 4..7 = over the
 // moved points (direction A); written by thread 0 in the scalar tail (and the prologue), read by every thread after barrier L6.
 constexpr int kAnchorFloats = kTermAnchorFloats + 4;   // [kTermAnchorFloats] = radius of the source cloud about the origin
+constexpr int kTermAges = 8;      // sm.anchor[kTermAges] as unsigned: 8 bits per metric, iterations in a row with a term dropped
+// Records of the term masks (term_anchor_masks, houv_math.h).  A term computed in the iteration that just ended has that
+// iteration's pose as its record pose: it is still in sm.pose when the rule runs.  At most one term per metric is older (it was
+// dropped): its record pose, 12 floats per metric, lives in the .w lanes of sm.tbox -- tile_boxes writes .w = 0 there once per
+// launch in the prologue, prune_masks reads x, y, z of a box only, and sm.tbox has 128 entries whatever the cloud size.
+constexpr int kStalePose = 4;     // floats between two consecutive entries of a stale pose (one float4 of sm.tbox each)
 
 
 // prune: 0 brute force, 2 pruned (balanced walk: + staging for block * q queries)
@@ -452,7 +465,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     sm.adam[(step & 1) * 2 + 1] = asc.bc2_sqrt;
   }
   if constexpr (PRUNE) {
-    // term masks: the first iteration of a launch computes every term (the anchor does not travel through `state`); the
+    // term masks: the first iteration of a launch computes every term (the records do not travel through `state`); the
     // radius of the source cloud about the origin is one max-reduce (a NaN or Inf coordinate gives +inf: no term is ever dropped)
     float r2 = 0.f;
 #pragma unroll
@@ -465,7 +478,10 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) r2 = fmaxf(r2, __shfl_xor(r2, o, 64));
     if ((tid & 63) == 0) sm.red[tid >> 6] = r2;
-    if (tid == 0) sm.ctl[0] = (int)(((1u << NMET) - 1u) * 0x11u);
+    if (tid == 0) {
+      sm.ctl[0] = (int)(((1u << NMET) - 1u) * 0x11u);
+      reinterpret_cast<unsigned*>(sm.anchor)[kTermAges] = 0u;
+    }
   }
   __syncthreads();
   if constexpr (PRUNE) {
@@ -488,7 +504,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   // is known); B's run exactly for the metrics B wins; a metric predicted B but won by A is repaired (rare).  Results do
   // not depend on the prediction.  The pruned kernel's bounds are distances to REMEMBERED nearest neighbours (nn_ws): any
   // remembered point gives a valid, attained bound, so a skipped rescan only leaves an older neighbour in place (a
-  // slightly looser bound); every kRefresh-th iteration rescans everything to keep them fresh.
+  // slightly looser bound); every kRefresh-th iteration rescans every term it computes to keep them fresh.
   unsigned pred_a = kAllMet;
   float* red_a = sm.red + ((size_t)1 * NW + (tid >> 6)) * kRedStride;
   float* red_b = sm.red + ((size_t)0 * NW + (tid >> 6)) * kRedStride;
@@ -496,7 +512,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   for (int it = 0; it < a.n_iters; ++it) {
     if (a.pred_mode == 1) pred_a = 0u;
     const bool allgrad = a.pred_mode == 2 || ((PRUNE != 0) && (((a.steps_done + it) % kRefresh) == 0 || (a.ws_valid == 0 && it == 0)));
-    // Term masks (term_masks, houv_math.h): a term that provably loses its metric's min is not computed -- no search, no
+    // Term masks (term_anchor_masks, houv_math.h): a term that provably loses its metric's min is not computed -- no search, no
     // selection, no sums, no rescans; its remembered NNs stay as they are (an older neighbour is still an attained bound).  The
     // proof also settles the prediction: where B's term is dropped A is the winner, and the other way round.  Workgroup-uniform.
     unsigned need_a = kAllMet, need_b = kAllMet;
@@ -505,7 +521,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       need_b = w & kAllMet;
       need_a = (w >> 4) & kAllMet;
     }
-    const unsigned grad_a = allgrad ? kAllMet : ((pred_a | ~need_b) & need_a);
+    const unsigned grad_a = (allgrad ? kAllMet : (pred_a | ~need_b)) & need_a;
     {
       // ---- move this lane's source points, publish them as references for sweep B ----
       float sx[Q], sy[Q], sz[Q], mx[Q], my[Q], mz[Q];
@@ -630,35 +646,54 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       if (it == a.n_iters - 1)
         store_outputs(a.out_score, a.out_loss, a.out_R, a.out_T, a.out_grad, a.out_cd, inst, f, r);
       if constexpr (PRUNE != 0) {
-        if ((need_a & need_b) == kAllMet) {   // every term was computed: this iteration is the anchor of the coming term masks
+        // every term computed in this iteration renews its record: its value here, its pose is this iteration's (sm.pose until
+        // the store below); a dropped term's record stays as it is
 #pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            sm.anchor[2 * m] = r.cd[m][0];
-            sm.anchor[2 * m + 1] = r.cd[m][1];
-          }
-#pragma unroll
-          for (int i = 0; i < 9; ++i) sm.anchor[8 + i] = f.R[i];
-#pragma unroll
-          for (int i = 0; i < 3; ++i) sm.anchor[17 + i] = f.T[i];
+        for (int m = 0; m < NMET; ++m) {
+          if ((need_b >> m) & 1u) sm.anchor[2 * m] = r.cd[m][0];
+          if ((need_a >> m) & 1u) sm.anchor[2 * m + 1] = r.cd[m][1];
         }
       }
       const int step = a.steps_done + it + 1;
       const AdamScalars asc{sm.adam[(step & 1) * 2 + 0], sm.adam[(step & 1) * 2 + 1]};
       solve_tail_step(r.g, sm.state, a.f64_params, asc, beta1, beta2, eps, angle_base, trans_mode, f);
-      store_pose(sm.pose, f);
       if constexpr (PRUNE != 0) {
-        // The coming iteration's term masks.  Every term is computed -- and so the anchor renewed -- on every kRefresh-th
-        // iteration, on the first iteration of a launch (prologue) and on the last one (its eight cd are outputs), and always
-        // under pred_mode 2; in between, term_masks drops what the anchor and the pose just stepped to prove unnecessary.
-        unsigned next = kAllMet | (kAllMet << 4);
-        const bool all_next = fresh(a.pred_mode) == 2 || ((a.steps_done + it + 1) % kRefresh) == 0 || it + 2 >= a.n_iters;
-        if (!all_next) next = term_masks<NMET>(sm.anchor, f.R, f.T, sm.anchor[kTermAnchorFloats]);
+        // The coming iteration's term masks.  Every term is computed on the first iteration of a launch (prologue), on the last
+        // one (its eight cd are outputs) and always under pred_mode 2; in between term_anchor_masks drops what the records and the
+        // pose just stepped to prove unnecessary (for at most kTermMaxAge iterations in a row where that is set).
+        unsigned next = kAllMet | (kAllMet << 4), ages = 0u;
+        const bool all_next = fresh(a.pred_mode) == 2 || it + 2 >= a.n_iters;
+        if (!all_next) {
+          const unsigned have = need_b | (need_a << 4);
+          float* stale = reinterpret_cast<float*>(sm.tbox) + 3;
+          next = term_anchor_masks<NMET>(sm.anchor, sm.pose, stale, kStalePose, ~have & 0xffu, f.R, f.T,
+                                         sm.anchor[kTermAnchorFloats]);
+          const unsigned old_ages = reinterpret_cast<const unsigned*>(sm.anchor)[kTermAges];
+#pragma unroll
+          for (int m = 0; m < NMET; ++m) {
+            unsigned age = (old_ages >> (8 * m)) & 0xffu;
+            age = (((next >> m) & (next >> (4 + m)) & 1u) != 0u) ? 0u : age + 1u;
+            if (kTermMaxAge > 0 && age > (unsigned)kTermMaxAge) {
+              next |= 0x11u << m;
+              age = 0u;
+            }
+            if (age > 0xffu) age = 0xffu;
+            ages |= age << (8 * m);
+            // a term computed in this iteration and dropped in the coming one: this iteration's pose becomes its stale record pose
+            if (((have & ~next) >> m) & 0x11u) {
+#pragma unroll
+              for (int i = 0; i < 12; ++i) stale[(m * 12 + i) * kStalePose] = sm.pose[i];
+            }
+          }
+        }
+        reinterpret_cast<unsigned*>(sm.anchor)[kTermAges] = ages;
         sm.ctl[0] = (int)next;
         if (a.stats) {
           atomicAdd(&a.stats[6], (unsigned long long)(__popc(need_a) + __popc(need_b)));
           atomicAdd(&a.stats[7], (unsigned long long)(2 * NMET));
         }
       }
+      store_pose(sm.pose, f);
       if (kAdamTid == 0 && it + 1 < a.n_iters) {                       // single-wave workgroups: no other wave to do it
         const AdamScalars nxt = adam_scalars(step + 1, lr, beta1, beta2);
         sm.adam[((step + 1) & 1) * 2 + 0] = nxt.step_size;
