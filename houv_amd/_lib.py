@@ -38,6 +38,7 @@ _SIGNATURES = {
     "houv_solve_variant": (ctypes.c_int, [_int, _int, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int)]),
     "houv_solve_lds_bytes": (ctypes.c_longlong, [_int, _int, _int]),
+    "houv_solve_walk_variant": (ctypes.c_int, [_int]),
     "houv_kd_sort": (ctypes.c_int, [_c_f, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_icp_refine": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _flt, _int, _flt, _flt, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_knn": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _c_f]),
@@ -109,6 +110,14 @@ def solve_variant(N, M, pruned=False, with_mode=False):
     check(load().houv_solve_variant(int(N), int(M), int(bool(pruned)), ctypes.byref(b), ctypes.byref(q), ctypes.byref(m)),
           "houv_solve_variant")
     return (b.value, q.value, m.value) if with_mode else (b.value, q.value)
+
+
+def solve_walk_variant(need):
+    """The compiled metric set (4 bits) that a pruned sweep with term mask `need` (0..15) runs on (houv_solve_walk_variant)."""
+    v = load().houv_solve_walk_variant(int(need))
+    if v < 0:
+        raise HouvHipError(f"houv_solve_walk_variant failed: {last_error()}")
+    return v
 
 
 def build_id():

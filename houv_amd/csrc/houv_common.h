@@ -33,12 +33,14 @@ inline bool check_launch(const char* what) {
 // independent of every switch except the two that select the matrix-pipe kernels (gemm_split, attn_split).
 //   "solve_predict"   0 normal; 1 always predict direction B (every A-win takes the repair path); 2 rescan everything
 //   "solve_stats"     device address of 8 uint64 counters the fused loop adds to (0 = off): see SolveArgs::stats
+//   "solve_walk_hist" device address of 16 uint64 counters (0 = off): the term masks the pruned walks see, see SolveArgs::walk_hist
 //   "knn_split"       houv_knn: 1 references split over the four waves of a workgroup (same lists), 0 the single-scan kernel
 //   "attn_split"      houv_attention_f32: 1 bf16 matrix pipe with three-part splits (full tiles), 0 fp32-input MFMA kernel
 //   "gemm_split"      houv_gemm_f32: 0 fp32-input MFMA, 6 / 3 = bf16 part products per fp32 product (gemm.hip, gemm_split_kernel)
 struct DebugKnobs {
   std::atomic<int> pred_mode{0};
   std::atomic<unsigned long long> stats{0ull};
+  std::atomic<unsigned long long> walk_hist{0ull};
   std::atomic<int> knn_split{1};         // houv_knn (N >= 512, k = 16 / 20): four waves per 64 queries, a quarter of the references each; 0: one wave per 64 queries
   std::atomic<int> attn_split{1};        // houv_attention_f32 on the bf16 matrix pipe (attention.hip, attention_split_kernel); 0: fp32-input MFMA
   std::atomic<int> gemm_split{6};        // houv_gemm_f32 on the bf16 matrix pipe: 6 / 3 part products per fp32 product (0: fp32-input MFMA)

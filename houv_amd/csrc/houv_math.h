@@ -388,6 +388,44 @@ HOUV_HD inline unsigned term_anchor_masks(const float* cd, const float* fresh, c
   return need;
 }
 
+// Walk variants of the pruned solve (houv_sweep.h, pruned_sweep_sorted).  A direction's four-bit `need` (one half of the word
+// above) selects code specialised at compile time for a metric set MSET: a metric outside MSET costs the box tests and the walk
+// nothing.  Any MSET that contains `need` is correct -- an extra metric is computed for nothing, as all of them were before -- so
+// only the sets of kWalkSets are instantiated and every other mask runs on the cheapest instantiated superset.  15 is always
+// present.  The sets were chosen from the histogram of the masks the walks see at 2,048 points (houv_debug_set("solve_walk_hist");
+// profiles/r12_walk_variants.txt): greedily by instructions removed under walk_step_cost, until the next set removes less than
+// 1 % of a walk step.  Each set is another copy of the box tests and of the walk at both sweep sites (+18 % code for five).
+constexpr int kWalkSets[] = {6, 11, 12, 13, 15};
+constexpr int kNumWalkSets = (int)(sizeof(kWalkSets) / sizeof(kWalkSets[0]));
+// VALU instructions of one walk step (a query against one 32-point sub-tile) that depend on the metric set: per two references
+// one fma per metric kept (metric 3's also feeds metric 0), the mul of y^2 for metric 1 alone, one min3 per metric; per step
+// five instructions of unit bookkeeping per metric.  The loads, the six subtractions and x^2 are common to all sets.
+constexpr int walk_step_cost(unsigned mset) {
+  const int k0 = (int)(mset & 1u), k1 = (int)((mset >> 1) & 1u), k2 = (int)((mset >> 2) & 1u), k3 = (int)((mset >> 3) & 1u);
+  return 16 * (2 * (k0 + k1 + k2 + ((k0 | k3) ? 1 : 0)) + 2 * k1 + (k0 + k1 + k2 + k3)) + 5 * (k0 + k1 + k2 + k3);
+}
+constexpr bool walk_instantiated(unsigned mset) {
+  for (int i = 0; i < kNumWalkSets; ++i)
+    if ((unsigned)kWalkSets[i] == mset) return true;
+  return false;
+}
+// the instantiated set that mask `need` (0..15) runs on: the cheapest one that contains it, the lowest set on a tie
+constexpr unsigned walk_variant(unsigned need) {
+  unsigned best = 15u;
+  for (int i = 0; i < kNumWalkSets; ++i) {
+    const unsigned s = (unsigned)kWalkSets[i];
+    if ((s & need) == need && walk_step_cost(s) < walk_step_cost(best)) best = s;
+  }
+  return best;
+}
+static_assert(walk_instantiated(15u) && walk_variant(15u) == 15u && walk_step_cost(15u) == 16 * 14 + 20, "today's code is a variant");
+// walk_variant() of all 16 masks, four bits each: what the kernel looks up with one scalar shift
+constexpr unsigned long long walk_variant_table() {
+  unsigned long long t = 0ull;
+  for (unsigned n = 0; n < 16u; ++n) t |= (unsigned long long)walk_variant(n) << (4 * n);
+  return t;
+}
+
 // ---------------------------------------------------------------------------------------------
 // 3x3 SVD by one-sided (Hestenes) Jacobi, register resident.  H = U diag(S) V^T, S sorted
 // descending like torch.svd (model_utils.py:233).

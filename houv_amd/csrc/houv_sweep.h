@@ -1,6 +1,8 @@
 // houv_sweep.h -- the LDS-broadcast brute-force nearest-neighbour sweep shared by the fused HOUV loop (solve.hip)
 // and the ICP refinement kernel (icp.hip), plus the workgroup reduction they both use.
 #pragma once
+#include <type_traits>
+
 #include "houv_common.h"
 
 namespace houv {
@@ -272,7 +274,10 @@ __device__ __forceinline__ unsigned lowest_bit_or_m1(unsigned x) {
 // order inside a tracking unit does not matter to a minimum.  ta = min(cb, first unit), tb = min(second unit).
 // NaN: v_min3 returns the minimum of its non-NaN operands, so a NaN distance never enters a chain and a chain that starts at a
 // number (cb is +inf or a distance, never NaN) ends at a number, as in sweep_tile().
-template <int NMET>
+// MSET (walk_variant, houv_math.h): bit m clear = metric m is not evaluated -- no fma of its own, no min3; cb[m], ta[m] and tb[m]
+// are neither read nor written, so they take no registers.  The metrics kept have the expression trees of the full set (metric 0
+// is still fma(az, az, a3) with a3 = fma(ay, ay, axx), whether metric 3 is kept or not): what is not used is simply not formed.
+template <int NMET, int MSET = (1 << NMET) - 1>
 __device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy, float cz, const float (&cb)[NMET],
                                                 float (&ta)[NMET], float (&tb)[NMET]) {
   constexpr int kBatch = 4, kHalf = kSub / 2;
@@ -295,10 +300,10 @@ __device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy,
       const float a1 = __builtin_fmaf(az, az, ayy), b1 = __builtin_fmaf(bz, bz, byy);
       const float a2 = __builtin_fmaf(az, az, axx), b2 = __builtin_fmaf(bz, bz, bxx);
       const float a0 = __builtin_fmaf(az, az, a3), b0 = __builtin_fmaf(bz, bz, b3);
-      t[0] = min3f(in[0], a0, b0);
-      t[1] = min3f(in[1], a1, b1);
-      t[2] = min3f(in[2], a2, b2);
-      t[3] = min3f(in[3], a3, b3);
+      if constexpr ((MSET & 1) != 0) t[0] = min3f(in[0], a0, b0);
+      if constexpr ((MSET & 2) != 0) t[1] = min3f(in[1], a1, b1);
+      if constexpr ((MSET & 4) != 0) t[2] = min3f(in[2], a2, b2);
+      if constexpr ((MSET & 8) != 0) t[3] = min3f(in[3], a3, b3);
     } else {
       t[0] = min3f(in[0], metric_sqdist<0>(ax, ay, az), metric_sqdist<0>(bx, by, bz));
     }
@@ -318,14 +323,21 @@ __device__ __forceinline__ void gather_tile_min(unsigned xa, float cx, float cy,
       eval2(r[1], r[3], tb, tb);
     }
   };
+  // A partial metric set pins the pipeline as written: the address of a batch's reads is made to depend (an empty asm, no
+  // instruction) on the evaluation before it.  Left alone, the scheduler fills the arithmetic a dropped metric frees with reads
+  // hoisted from later batches, 4 VGPRs each: the three-metric loops took up to 19 VGPRs MORE than the full one and spilled what
+  // lives across the walk.  The full set keeps the schedule it had.
+  constexpr bool kPin = NMET == 4 && MSET != (1 << NMET) - 1;
   float4 ra[kBatch], rb[kBatch];
   fetch(ra, 0);
 #pragma unroll
   for (int i0 = 0; i0 < kHalf; i0 += kBatch) {
     fetch(rb, i0 + kBatch / 2);
     eval(ra, i0 == 0);
+    if constexpr (kPin) asm volatile("" : "+v"(xa));
     if (i0 + kBatch < kHalf) fetch(ra, i0 + kBatch);
     eval(rb, false);
+    if constexpr (kPin) asm volatile("" : "+v"(xa));
   }
 }
 
@@ -342,7 +354,10 @@ __device__ __forceinline__ void take_units(float ta, float tb, int unit0, float&
 // query's nearest neighbour in the previous iteration (`prev`, attained), the test a point-to-box distance per metric.
 // `need` (workgroup-uniform; term_masks, houv_math.h): bit m clear = this direction's term of metric m provably loses the min
 // and is not computed: its bound is -1, so no box passes on its account and the lists shrink.
-template <int BLOCK, int Q, int NMET>
+// MSET (a compile-time superset of `need`; walk_variant, houv_math.h): a metric outside it has no remembered-neighbour distance, no
+// box distance, no compare and no OR.  Its verdict was "no box passes" before (bound -1 against a distance >= 0 or NaN), so the
+// masks are the same bits.  A metric inside MSET but outside `need` keeps the run-time bound -1.
+template <int BLOCK, int Q, int NMET, int MSET = (1 << NMET) - 1>
 __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                             const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
                                             buf_t ws, int prev_off, int count, unsigned need,
@@ -362,15 +377,15 @@ __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, con
         w0 = __builtin_amdgcn_raw_buffer_load_b32(ws, voff, soff, 0);
       }
     }
-    { const float4 r = refs[w0 & 0xffffu]; ub[k][0] = metric_sqdist<0>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+    if constexpr ((MSET & 1) != 0) { const float4 r = refs[w0 & 0xffffu]; ub[k][0] = metric_sqdist<0>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
     if constexpr (NMET == 4) {
-      { const float4 r = refs[w0 >> 16]; ub[k][1] = metric_sqdist<1>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
-      { const float4 r = refs[w1 & 0xffffu]; ub[k][2] = metric_sqdist<2>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
-      { const float4 r = refs[w1 >> 16]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      if constexpr ((MSET & 2) != 0) { const float4 r = refs[w0 >> 16]; ub[k][1] = metric_sqdist<1>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      if constexpr ((MSET & 4) != 0) { const float4 r = refs[w1 & 0xffffu]; ub[k][2] = metric_sqdist<2>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
+      if constexpr ((MSET & 8) != 0) { const float4 r = refs[w1 >> 16]; ub[k][3] = metric_sqdist<3>(r.x - qx[k], r.y - qy[k], r.z - qz[k]); }
     }
 #pragma unroll
     for (int m = 0; m < NMET; ++m)   // box distances are rounded: stay conservative
-      ub[k][m] = (ok && ((need >> m) & 1u)) ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;
+      if ((MSET >> m) & 1) ub[k][m] = (ok && ((need >> m) & 1u)) ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;
   }
   unsigned alo[Q], ahi[Q];
 #pragma unroll
@@ -389,8 +404,11 @@ __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, con
         const float xx = dx * dx, yy = dy * dy;
         const float s3 = __builtin_fmaf(dy, dy, xx), s1 = __builtin_fmaf(dz, dz, yy), s2 = __builtin_fmaf(dz, dz, xx);
         const float s0 = __builtin_fmaf(dz, dz, s3);
-        in = __builtin_amdgcn_ballot_w64(s0 <= ub[k][0]) | __builtin_amdgcn_ballot_w64(s1 <= ub[k][1]) |
-             __builtin_amdgcn_ballot_w64(s2 <= ub[k][2]) | __builtin_amdgcn_ballot_w64(s3 <= ub[k][3]);
+        in = 0ull;                                        // s3 is still formed where s0 needs it
+        if constexpr ((MSET & 1) != 0) in |= __builtin_amdgcn_ballot_w64(s0 <= ub[k][0]);
+        if constexpr ((MSET & 2) != 0) in |= __builtin_amdgcn_ballot_w64(s1 <= ub[k][1]);
+        if constexpr ((MSET & 4) != 0) in |= __builtin_amdgcn_ballot_w64(s2 <= ub[k][2]);
+        if constexpr ((MSET & 8) != 0) in |= __builtin_amdgcn_ballot_w64(s3 <= ub[k][3]);
       } else {
         in = __builtin_amdgcn_ballot_w64(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) <= ub[k][0]);
       }
@@ -440,18 +458,45 @@ __device__ __forceinline__ unsigned& w_slot(float4* cloud, int q) { return reint
 // after the walk, the tracking-unit ids (8 bits each: <= 256 units of 16 references) of its minima; .w of whi[q] the high half.
 // TS = 1 (clouds of 2049..4096 points): the masks are over 64 SUPER-tiles of two sub-tiles each (`boxes`, `ntile` count
 // super-tiles); a visit evaluates both sub-tiles in ascending order, the minima carry tracking-unit ids (0..255) for the rescans.
-// `need`: see prune_masks; (best, btile) of a metric whose bit is clear are garbage (the minimum over another metrics' lists).
+// `need`: see prune_masks; (best, btile) of a metric whose bit is clear are never read downstream (select_all, park_sqrt_sums,
+// park_grad_sums and final_sums skip on `need`): +inf and unit 0 where the walk variant leaves the metric out, the minimum over
+// the other metrics' lists where a superset variant computes it.
+// Walk variants: `need` is workgroup-uniform, so it selects -- with one scalar table look-up (walk_variant, houv_math.h) and one
+// switch each -- box tests and a block loop compiled for the metric set MSET.  The counting sort and the barriers S1..S3 between
+// the two are common code: every wave meets the same barriers whichever variant it runs.
+// `walk_hist` (houv_debug_set("solve_walk_hist")): 16 counters, +1 in slot `need` per wave and sweep; null = off.
+template <typename F>
+__device__ __forceinline__ void walk_dispatch(unsigned mset, F&& f) {
+#define HOUV_WALK_CASE(S)                                                          \
+  case S:                                                                          \
+    if constexpr (walk_instantiated(S)) f(std::integral_constant<int, S>{});       \
+    break;
+  switch (mset) {   // mset = walk_variant(need): always one of the instantiated sets
+    HOUV_WALK_CASE(1) HOUV_WALK_CASE(2) HOUV_WALK_CASE(3) HOUV_WALK_CASE(4) HOUV_WALK_CASE(5) HOUV_WALK_CASE(6) HOUV_WALK_CASE(7)
+    HOUV_WALK_CASE(8) HOUV_WALK_CASE(9) HOUV_WALK_CASE(10) HOUV_WALK_CASE(11) HOUV_WALK_CASE(12) HOUV_WALK_CASE(13) HOUV_WALK_CASE(14)
+    default: f(std::integral_constant<int, 15>{}); break;
+  }
+#undef HOUV_WALK_CASE
+}
+
 template <int BLOCK, int Q, int NMET, int TS = 0>
 __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
                                                     const float4* __restrict__ qarr, float4* wlo, float4* whi,
                                                     const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
-                                                    buf_t ws, int prev_off, int count, unsigned need, int rot,
+                                                    buf_t ws, int prev_off, int count, unsigned need,
                                                     const SortedStage& st, float4* __restrict__ res, float (&best)[Q][NMET],
-                                                    int (&btile)[Q][NMET], unsigned long long* __restrict__ stats) {
+                                                    int (&btile)[Q][NMET], unsigned long long* __restrict__ stats,
+                                                    unsigned long long* __restrict__ walk_hist) {
   static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "whole waves; thread 64 resets the block counter");
   const int tid = tid_x(), lane = tid & 63;
   unsigned long long un[Q];
-  prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, need, un);
+  if constexpr (NMET == 4) {
+    walk_dispatch((unsigned)(walk_variant_table() >> (4u * need)) & 15u, [&](auto mset) {
+      prune_masks<BLOCK, Q, NMET, decltype(mset)::value>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, need, un);
+    });
+  } else {
+    prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, need, un);
+  }
   int len[Q], rnk[Q];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
@@ -487,54 +532,62 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
   if (tid < 65) st.hist[tid] = 0;
   const int nblk = (count + 63) >> 6;
   int asked = 0, nsteps = 0;
-  for (;;) {
-    int b = 0;
-    if (lane == 0) b = atomicAdd(&st.hist[130], 1);
-    b = __builtin_amdgcn_readfirstlane(b);
-    if (b >= nblk) break;
-    const int e = b * 64 + lane;
-    const bool valid = e < count;                                       // the last block may be partly filled
-    const int q = st.order[valid ? e : count - 1];
-    unsigned long long mm = valid ? (((unsigned long long)w_slot(whi, q) << 32) | w_slot(wlo, q)) : 0ull;
-    const int cap = __builtin_amdgcn_readfirstlane(__popcll(mm));      // sorted: lane 0 holds the block's longest list
-    const float4 qp = qarr[q];
-    float cb[NMET];
-    int ct[NMET];
+  auto walk_blocks = [&](auto mset) {
+    constexpr int MSET = decltype(mset)::value;
+    for (;;) {
+      int b = 0;
+      if (lane == 0) b = atomicAdd(&st.hist[130], 1);
+      b = __builtin_amdgcn_readfirstlane(b);
+      if (b >= nblk) break;
+      const int e = b * 64 + lane;
+      const bool valid = e < count;                                       // the last block may be partly filled
+      const int q = st.order[valid ? e : count - 1];
+      unsigned long long mm = valid ? (((unsigned long long)w_slot(whi, q) << 32) | w_slot(wlo, q)) : 0ull;
+      const int cap = __builtin_amdgcn_readfirstlane(__popcll(mm));      // sorted: lane 0 holds the block's longest list
+      const float4 qp = qarr[q];
+      float cb[NMET];
+      int ct[NMET];
 #pragma unroll
-    for (int m = 0; m < NMET; ++m) { cb[m] = INFINITY; ct[m] = 0; }
-    asked += __popcll(mm);
-    nsteps += cap;
-    // the lane's rotated base address, kept across the steps: a step forms its sub-tile's address with one shift-add
-    const unsigned xbase = (unsigned)(size_t)(lds_f4)refs + (((unsigned)rot & 15u) << 4);
-    int t = 0;
+      for (int m = 0; m < NMET; ++m) { cb[m] = INFINITY; ct[m] = 0; }
+      asked += __popcll(mm);
+      nsteps += cap;
+      // the lane's rotated base address, kept across the steps: a step forms its sub-tile's address with one shift-add
+      // (from the opaque thread index, like everything else the iteration loop derives per lane: see tid_x)
+      const unsigned xbase = (unsigned)(size_t)(lds_f4)refs + (((unsigned)tid_x() & 15u) << 4);
+      int t = 0;
 #pragma unroll 1
-    for (int s = 0; s < cap; ++s) {
-      // next sub-tile = lowest set bit, found on the 32-bit halves: v_ffbl gives -1 for an empty word, so the lower of
-      // (lo, 32 | hi) as unsigned is the next sub-tile, or -1 for an empty list, which the signed max with t turns into "stay"
-      // (lists ascend: the next sub-tile is above t, and the first one is >= 0 = t).  No 64-bit compare, no select.
-      const unsigned nxt = min(lowest_bit_or_m1((unsigned)mm), lowest_bit_or_m1((unsigned)(mm >> 32)) | 32u);
-      t = max(t, (int)nxt);
-      mm &= mm - 1ull;                                                  // 0 stays 0
+      for (int s = 0; s < cap; ++s) {
+        // next sub-tile = lowest set bit, found on the 32-bit halves: v_ffbl gives -1 for an empty word, so the lower of
+        // (lo, 32 | hi) as unsigned is the next sub-tile, or -1 for an empty list, which the signed max with t turns into "stay"
+        // (lists ascend: the next sub-tile is above t, and the first one is >= 0 = t).  No 64-bit compare, no select.
+        const unsigned nxt = min(lowest_bit_or_m1((unsigned)mm), lowest_bit_or_m1((unsigned)(mm >> 32)) | 32u);
+        t = max(t, (int)nxt);
+        mm &= mm - 1ull;                                                  // 0 stays 0
 #pragma unroll
-      for (int h = 0; h < (1 << TS); ++h) {
-        const int ts = (t << TS) | h;                                   // sub-tile
-        const unsigned xa = xbase + (unsigned)ts * (kSub * 16u);
-        float ta[NMET], tb[NMET];                                       // ta: the running minima threaded through the first tracking unit
-        gather_tile_min<NMET>(xa, qp.x, qp.y, qp.z, cb, ta, tb);
+        for (int h = 0; h < (1 << TS); ++h) {
+          const int ts = (t << TS) | h;                                   // sub-tile
+          const unsigned xa = xbase + (unsigned)ts * (kSub * 16u);
+          float ta[NMET], tb[NMET];                                       // ta: the running minima threaded through the first tracking unit
+          gather_tile_min<NMET, MSET>(xa, qp.x, qp.y, qp.z, cb, ta, tb);
 #pragma unroll
-        for (int m = 0; m < NMET; ++m) take_units(ta[m], tb[m], 2 * ts, cb[m], ct[m]);
+          for (int m = 0; m < NMET; ++m)
+            if ((MSET >> m) & 1) take_units(ta[m], tb[m], 2 * ts, cb[m], ct[m]);
+        }
+      }
+      if (valid) {   // a metric outside MSET goes back as it was initialised: +inf, unit 0
+        if constexpr (NMET == 4) {
+          res[q] = make_float4(cb[0], cb[1], cb[2], cb[3]);
+          w_slot(wlo, q) = (unsigned)ct[0] | ((unsigned)ct[1] << 8) | ((unsigned)ct[2] << 16) | ((unsigned)ct[3] << 24);
+        } else {
+          res[q].x = cb[0];
+          w_slot(wlo, q) = (unsigned)ct[0];
+        }
       }
     }
-    if (valid) {
-      if constexpr (NMET == 4) {
-        res[q] = make_float4(cb[0], cb[1], cb[2], cb[3]);
-        w_slot(wlo, q) = (unsigned)ct[0] | ((unsigned)ct[1] << 8) | ((unsigned)ct[2] << 16) | ((unsigned)ct[3] << 24);
-      } else {
-        res[q].x = cb[0];
-        w_slot(wlo, q) = (unsigned)ct[0];
-      }
-    }
-  }
+  };
+  if constexpr (NMET == 4) walk_dispatch((unsigned)(walk_variant_table() >> (4u * need)) & 15u, walk_blocks);
+  else walk_blocks(std::integral_constant<int, 1>{});
+  if (walk_hist && lane == 0) atomicAdd(&walk_hist[need & 15u], 1ull);   // the unit of stats[2]
   if (stats) {
     asked = wave_incl_scan_dpp(asked);
     if (lane == 63) atomicAdd(&stats[0], (unsigned long long)asked);
@@ -573,6 +626,10 @@ __device__ __forceinline__ void tile_boxes(const float (&x)[Q], const float (&y)
                                            int ntile, float4* __restrict__ box) {
   constexpr int kTile = kSub << TS;
   static_assert(kTile <= 64, "a tile's owners must sit in one wave");
+  // xor-shuffle over the tile's lanes, the partner's address formed here from the opaque thread index: __shfl_xor's (from the
+  // lane id) were hoisted out of the iteration loop, one VGPR per offset held for the whole kernel
+  const int lane4 = tid_x() << 2;
+  auto shfl_xor = [&](float v, int o) { return __int_as_float(__builtin_amdgcn_ds_bpermute((lane4 ^ (o << 2)) & 252, __float_as_int(v))); };
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
     float lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY;
@@ -582,8 +639,8 @@ __device__ __forceinline__ void tile_boxes(const float (&x)[Q], const float (&y)
     }
 #pragma unroll
     for (int o = 1; o < kTile; o <<= 1) {
-      lx = fminf(lx, __shfl_xor(lx, o, 64)); ly = fminf(ly, __shfl_xor(ly, o, 64)); lz = fminf(lz, __shfl_xor(lz, o, 64));
-      hx = fmaxf(hx, __shfl_xor(hx, o, 64)); hy = fmaxf(hy, __shfl_xor(hy, o, 64)); hz = fmaxf(hz, __shfl_xor(hz, o, 64));
+      lx = fminf(lx, shfl_xor(lx, o)); ly = fminf(ly, shfl_xor(ly, o)); lz = fminf(lz, shfl_xor(lz, o));
+      hx = fmaxf(hx, shfl_xor(hx, o)); hy = fmaxf(hy, shfl_xor(hy, o)); hz = fmaxf(hz, shfl_xor(hz, o));
     }
     const int t = pt_index<BLOCK>(k) / kTile;
     if ((tid_x() % kTile) == 0 && t < ntile) {

@@ -47,6 +47,8 @@ struct SolveArgs : SolveCommon {
                                // [4] shader clocks (s_memtime) and [5] 100-MHz ticks (s_memrealtime) summed over the workgroups'
                                // loops: [4]/[5] x 100 MHz = the clock the chip sustained under THIS kernel's load; pruned kernels:
                                // [6] Chamfer terms computed and [7] terms possible (2 x metrics), per workgroup-iteration
+  unsigned long long* walk_hist;   // houv_debug_set("solve_walk_hist", device pointer): 16 counters, slot = the term mask `need` of a
+                                   // pruned sweep, +1 per walking wave (the unit of stats[2]); read where it is used only (fresh)
 };
 
 constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS reads (recover_nn)
@@ -429,7 +431,6 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   }
   int hrot = 0;
   __syncthreads();
-  const int rot = tid & (kSub - 1);
   // this hypothesis' workspace (pruned mode; brute force: src again, never accessed): byte offsets of the NN records of
   // direction 0 (NN of the target points in the moved cloud) and direction 1 (NN of the moved points in the target)
   buf_t ws = src;
@@ -506,8 +507,9 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   // remembered point gives a valid, attained bound, so a skipped rescan only leaves an older neighbour in place (a
   // slightly looser bound); every kRefresh-th iteration rescans every term it computes to keep them fresh.
   unsigned pred_a = kAllMet;
-  float* red_a = sm.red + ((size_t)1 * NW + (tid >> 6)) * kRedStride;
-  float* red_b = sm.red + ((size_t)0 * NW + (tid >> 6)) * kRedStride;
+  // this wave's row of the reduction scratch of a direction, formed where it is used from the opaque thread index (formed here,
+  // once, the two addresses lived in VGPRs through every walk of the loop)
+  auto red_row = [&](int dir) { return sm.red + ((size_t)dir * NW + (tid_x() >> 6)) * kRedStride; };
 #pragma unroll 1
   for (int it = 0; it < a.n_iters; ++it) {
     if (a.pred_mode == 1) pred_a = 0u;
@@ -517,7 +519,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     // proof also settles the prediction: where B's term is dropped A is the winner, and the other way round.  Workgroup-uniform.
     unsigned need_a = kAllMet, need_b = kAllMet;
     if constexpr (PRUNE != 0) {
-      const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(sm.ctl[0]);
+      const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(fresh_lds(reinterpret_cast<const float*>(sm.ctl))));
       need_b = w & kAllMet;
       need_a = (w >> 4) & kAllMet;
     }
@@ -548,7 +550,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         if (pruned_now) {
           if constexpr (PRUNE != 0)
             pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
-                                                need_a, rot, sm.st, ws_res, best, btile, a.stats);
+                                                need_a, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist));
         } else {
           sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
           if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
@@ -556,11 +558,11 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         // ---- epilogue A: selection, S of every needed metric, G/GP of the predicted-A metrics; one barrier ----
         unsigned sel[NMET];
         select_all<BLOCK, Q, NMET>(sm, best, N, a.k_full, a.k_view, need_a, hrot, sel);
-        park_sqrt_sums<BLOCK, Q, NMET>(best, sel, need_a, red_a);
-        park_grad_sums<BLOCK, Q, NMET, 1, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_a, ws,
+        park_sqrt_sums<BLOCK, Q, NMET>(best, sel, need_a, red_row(1));
+        park_grad_sums<BLOCK, Q, NMET, 1, PRUNE != 0>(sm, sm.tgt, mx, my, mz, best, btile, sel, grad_a, N, sx, sy, sz, red_row(1), ws,
                                                      ws_a);
       }
-      __syncthreads();   // L2 -- writers: every wave's parked partials of direction A (red_a); readers: wave 0's final_sums
+      __syncthreads();   // L2 -- writers: every wave's parked partials of direction A (red_row(1)); readers: wave 0's final_sums
       final_sums<BLOCK, NMET>(sm, 1, true, grad_a, need_a);
     }
     unsigned pick_a;
@@ -578,7 +580,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       // workgroup-uniform, so all waves meet in the same pair).  Written twice so that B's minima are scoped to the branch that
       // computes them: as values merged after a skipped sweep they were carried around the iteration loop, in spilled VGPRs.
       auto pick_winners = [&]() {
-        __syncthreads();   // L3 -- writers: every wave's parked S of direction B (red_b); readers: wave 0's final_sums
+        __syncthreads();   // L3 -- writers: every wave's parked S of direction B (red_row(0)); readers: wave 0's final_sums
         final_sums<BLOCK, NMET>(sm, 0, true, 0u, need_b);
         __syncthreads();   // L4 -- writers: wave 0's S of both directions (sm.acc; A's since L2); readers: every thread's picked_direction
         pick_a = picked_direction<NMET>(sm, fresh(a.k_full), fresh(a.k_view));
@@ -591,7 +593,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         if (pruned_now) {
           if constexpr (PRUNE != 0)
             pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
-                                                need_b, rot, sm.st, ws_res, best, btile, a.stats);
+                                                need_b, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist));
         } else {
           sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
           if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
@@ -599,9 +601,9 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         // ---- epilogue B: selection and S first; then the winners are known to every thread ----
         unsigned sel[NMET];
         select_all<BLOCK, Q, NMET>(sm, best, M, a.k_full, a.k_view, need_b, hrot, sel);
-        park_sqrt_sums<BLOCK, Q, NMET>(best, sel, need_b, red_b);
+        park_sqrt_sums<BLOCK, Q, NMET>(best, sel, need_b, red_row(0));
         grad_b = pick_winners();
-        park_grad_sums<BLOCK, Q, NMET, 0, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_b, ws,
+        park_grad_sums<BLOCK, Q, NMET, 0, PRUNE != 0>(sm, sm.mov, tx, ty, tz, best, btile, sel, grad_b, M, tx, ty, tz, red_row(0), ws,
                                                      ws_b);
       } else {   // none of B's terms needed: every metric's winner is A, proven
         pick_winners();
@@ -609,11 +611,11 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       // ---- repair: won by A, but A's rescans were skipped ----
       const unsigned miss = pick_a & ~grad_a & kAllMet;
       if (miss) {
-        if (miss & 1u) repair_direction_a<BLOCK, Q, 0>(sm, src, N, mpad, a.k_full, hrot, red_a);
+        if (miss & 1u) repair_direction_a<BLOCK, Q, 0>(sm, src, N, mpad, a.k_full, hrot, red_row(1));
         if constexpr (NMET == 4) {
-          if (miss & 2u) repair_direction_a<BLOCK, Q, 1>(sm, src, N, mpad, a.k_view, hrot, red_a);
-          if (miss & 4u) repair_direction_a<BLOCK, Q, 2>(sm, src, N, mpad, a.k_view, hrot, red_a);
-          if (miss & 8u) repair_direction_a<BLOCK, Q, 3>(sm, src, N, mpad, a.k_view, hrot, red_a);
+          if (miss & 2u) repair_direction_a<BLOCK, Q, 1>(sm, src, N, mpad, a.k_view, hrot, red_row(1));
+          if (miss & 4u) repair_direction_a<BLOCK, Q, 2>(sm, src, N, mpad, a.k_view, hrot, red_row(1));
+          if (miss & 8u) repair_direction_a<BLOCK, Q, 3>(sm, src, N, mpad, a.k_view, hrot, red_row(1));
         }
       }
       __syncthreads();   // L5 -- writers: every wave's parked G / GP of direction B and of the repairs; readers: wave 0's final_sums
@@ -777,6 +779,14 @@ extern "C" int houv_solve_variant(int N, int M, int pruned, int* block, int* poi
   return 1;
 }
 
+extern "C" int houv_solve_walk_variant(int need) {
+  if (need < 0 || need > 15) {
+    houv::set_error("houv_solve_walk_variant: the term mask of a direction is 0..15, got %d", need);
+    return -1;
+  }
+  return (int)houv::walk_variant((unsigned)need);
+}
+
 extern "C" long long houv_solve_lds_bytes(int N, int M, int pruned) {
   using namespace houv;
   int block = 0, q = 0, mode = 0;
@@ -818,7 +828,8 @@ static int solve_dispatch(const houv::SolveCommon& c, int use_views, short* nn_w
   const int N = c.N, M = c.M;
   // pred_mode / stats are diagnostics set through houv_debug_set(), never through the environment.
   SolveArgs a{c, nn_ws, ws_valid, ws_stride, g_debug.pred_mode.load(),
-              reinterpret_cast<unsigned long long*>(g_debug.stats.load())};
+              reinterpret_cast<unsigned long long*>(g_debug.stats.load()),
+              reinterpret_cast<unsigned long long*>(g_debug.walk_hist.load())};
   hipStream_t s = (hipStream_t)stream;
   const int mx = N > M ? N : M;
   int block = 0, q = 0, mode = 0;

@@ -163,6 +163,13 @@ int houv_solve_variant(int N, int M, int pruned, int* block, int* points_per_lan
  * still share a CU's 160 KiB. */
 long long houv_solve_lds_bytes(int N, int M, int pruned);
 
+/* The pruned four-metric kernels compile their box tests and their walk for a few metric sets only.  `need` (0..15, bit m = this
+ * direction's Chamfer term of metric m is computed in this iteration) runs on the returned set: a superset of `need`, 15 = all
+ * four metrics (host-only query, no GPU work; -1 with houv_last_error() set for a mask outside 0..15).  Results do not depend on
+ * the table.  houv_debug_set("solve_walk_hist", address of 16 uint64 on the device) counts the masks the walks see.
+ * No counterpart in the reference; exported so that the test-suite can prove that every compiled set is exercised. */
+int houv_solve_walk_variant(int need);
+
 /* The point order houv_solve_iterate_pruned wants, on the device: every cloud reordered so that consecutive runs of `leaf` points
  * are the leaves of a balanced k-d tree -- bit for bit the permutation of houv_amd.solver.kd_sort (torch) on the same device.
  * Lexicographic (x, y, z) start; then, level by level, every range of more than one tile (tiles = ceil(len / leaf)) is cut at
