@@ -73,6 +73,10 @@ extern "C" int houv_debug_set(const char* name, long long value) {
     g_debug.walk_hist = (unsigned long long)value;
     return 1;
   }
+  if (name && !strcmp(name, "solve_cull_stats")) {
+    g_debug.cull_stats = (unsigned long long)value;
+    return 1;
+  }
   for (const auto& k : ints)
     if (name && !strcmp(name, k.name) && value >= k.lo && value <= k.hi && value % k.step == 0) {
       *k.knob = (int)value;

@@ -34,6 +34,7 @@ inline bool check_launch(const char* what) {
 //   "solve_predict"   0 normal; 1 always predict direction B (every A-win takes the repair path); 2 rescan everything
 //   "solve_stats"     device address of 8 uint64 counters the fused loop adds to (0 = off): see SolveArgs::stats
 //   "solve_walk_hist" device address of 16 uint64 counters (0 = off): the term masks the pruned walks see, see SolveArgs::walk_hist
+//   "solve_cull_stats" device address of 4 uint64 counters (0 = off): the group cull of the box tests, see SolveArgs::cull_stats
 //   "knn_split"       houv_knn: 1 references split over the four waves of a workgroup (same lists), 0 the single-scan kernel
 //   "attn_split"      houv_attention_f32: 1 bf16 matrix pipe with three-part splits (full tiles), 0 fp32-input MFMA kernel
 //   "gemm_split"      houv_gemm_f32: 0 fp32-input MFMA, 6 / 3 = bf16 part products per fp32 product (gemm.hip, gemm_split_kernel)
@@ -41,6 +42,7 @@ struct DebugKnobs {
   std::atomic<int> pred_mode{0};
   std::atomic<unsigned long long> stats{0ull};
   std::atomic<unsigned long long> walk_hist{0ull};
+  std::atomic<unsigned long long> cull_stats{0ull};
   std::atomic<int> knn_split{1};         // houv_knn (N >= 512, k = 16 / 20): four waves per 64 queries, a quarter of the references each; 0: one wave per 64 queries
   std::atomic<int> attn_split{1};        // houv_attention_f32 on the bf16 matrix pipe (attention.hip, attention_split_kernel); 0: fp32-input MFMA
   std::atomic<int> gemm_split{6};        // houv_gemm_f32 on the bf16 matrix pipe: 6 / 3 part products per fp32 product (0: fp32-input MFMA)
@@ -107,6 +109,22 @@ __device__ __forceinline__ int wave_max_to_lane63(int v) {
   v = max(v, dpp_i<0x118>(v));
   v = max(v, dpp_i<0x142, 0xa>(v));
   v = max(v, dpp_i<0x143, 0xc>(v));
+  return v;
+}
+
+// Maximum of floats over the 64 lanes, NaN left out (all NaN: NaN), valid in LANE 63 ONLY.  Any sign: a masked-out or
+// out-of-row DPP source reads the lane's own value, not 0.
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ float fmax_dpp(float v) {
+  return __builtin_fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false)));
+}
+__device__ __forceinline__ float wave_fmax_to_lane63(float v) {
+  v = fmax_dpp<0x111>(v);
+  v = fmax_dpp<0x112>(v);
+  v = fmax_dpp<0x114>(v);
+  v = fmax_dpp<0x118>(v);
+  v = fmax_dpp<0x142, 0xa>(v);
+  v = fmax_dpp<0x143, 0xc>(v);
   return v;
 }
 

@@ -427,6 +427,80 @@ constexpr unsigned long long walk_variant_table() {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Box tests of the pruned solve (houv_sweep.h, prune_masks) and their cull per GROUP of queries.
+//
+// Per query and reference box the kernel asks: is the box, for some metric m of the set, no farther from the query than the
+// query's bound ub[m]?  box_test_query restates that test for the host, instruction for instruction: the offset per axis is the
+// query minus the query clamped into the box (v_med3_f32), squared and summed per metric in the order of metric_sqdist, `<=`.
+//
+// box_test_group is the same question for a whole group of queries at once -- the 64 queries of one k of a wave, two k-d leaves
+// of a sorted cloud -- and is the code the kernel runs: the group's box [glo, ghi] (min / max of the queries' coordinates, NaN
+// left out) against the reference box, with the group's LARGEST bound per metric (NaN left out).  A box that fails it fails the
+// test of every query of the group, so the per-query tests run over the surviving boxes only and give the bits they gave before.
+//
+// Why it is exact, not merely safe in exact arithmetic:
+//   * fp32 subtraction, multiplication and fma round monotonically in each operand.
+//   * With L = min(lo, hi), H = max(lo, hi) of the reference box on an axis (the clamp takes its bounds in either order), a
+//     query's offset is |q - med3(q, lo, hi)| = max(fl(L - q), fl(q - H), 0): fl(a - b) = -fl(b - a), and the sign is squared
+//     away.  For glo <= q <= ghi, fl(L - q) >= fl(L - ghi) and fl(q - H) >= fl(glo - H): the offset is >= the group's gap
+//     g = max(fl(L - ghi), fl(glo - H), 0) on every axis.
+//   * The same mul / fma tree over non-negative operands, each >= the group's: s_m(query) >= s_m(group) in fp32.
+//   * ub[m] of the query <= the group's bound.  So s_m(group) > bound, for every m of the set, gives s_m(query) > ub[m]: fail.
+//   * NaN: a gap is never NaN (the maxima leave NaN out; Inf - Inf on one side leaves the other side or 0: a smaller gap, which
+//     only lets a box survive), so neither is s_m(group).  The group box is formed per axis, and a NaN coordinate is left out
+//     of its own axis only: a query with a NaN on an axis has a NaN offset there and fails every metric that reads the axis, as
+//     before; a view that drops the axis reads the other two, on which the query IS inside the group box, and the argument
+//     above holds for it.  A NaN bound passes nothing in either test; the group's bound is NaN only when every query's is.
+// ---------------------------------------------------------------------------------------------
+// v_med3_f32: the median of three numbers; with a NaN among them, the minimum of the others
+HOUV_HD inline float box_med3(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_fmed3f(a, b, c);
+#else
+  if (a != a || b != b || c != c) return fminf(fminf(a, b), c);
+  return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+#endif
+}
+
+// s_m of the offsets (dx, dy, dz) for the metrics of `mset` against the bounds b[m]: the expression trees of prune_masks
+template <int NMET>
+HOUV_HD inline bool box_within_bounds(float dx, float dy, float dz, const float* b, unsigned mset) {
+  if constexpr (NMET == 4) {
+    const float xx = dx * dx, yy = dy * dy;
+    const float s3 = __builtin_fmaf(dy, dy, xx), s1 = __builtin_fmaf(dz, dz, yy), s2 = __builtin_fmaf(dz, dz, xx);
+    const float s0 = __builtin_fmaf(dz, dz, s3);
+    bool in = false;
+    if (mset & 1u) in |= s0 <= b[0];
+    if (mset & 2u) in |= s1 <= b[1];
+    if (mset & 4u) in |= s2 <= b[2];
+    if (mset & 8u) in |= s3 <= b[3];
+    return in;
+  } else {
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) <= b[0];
+  }
+}
+
+// the per-query test, restated (q, lo, hi: x, y, z; ub: one bound per metric, -1 = the metric's term is not computed)
+template <int NMET>
+HOUV_HD inline bool box_test_query(const float* q, const float* lo, const float* hi, const float* ub, unsigned mset) {
+  return box_within_bounds<NMET>(q[0] - box_med3(q[0], lo[0], hi[0]), q[1] - box_med3(q[1], lo[1], hi[1]),
+                                 q[2] - box_med3(q[2], lo[2], hi[2]), ub, mset);
+}
+
+// gap between the group's interval [glo, ghi] and the box's, whichever way round its bounds are; never NaN
+HOUV_HD inline float box_group_gap(float glo, float ghi, float lo, float hi) {
+  return fmaxf(fmaxf(fminf(lo, hi) - ghi, glo - fmaxf(lo, hi)), 0.0f);
+}
+
+// the group verdict: false = no query inside [glo, ghi] with bounds <= gub passes box_test_query on this box
+template <int NMET>
+HOUV_HD inline bool box_test_group(const float* glo, const float* ghi, const float* lo, const float* hi, const float* gub,
+                                   unsigned mset) {
+  return box_within_bounds<NMET>(box_group_gap(glo[0], ghi[0], lo[0], hi[0]), box_group_gap(glo[1], ghi[1], lo[1], hi[1]),
+                                 box_group_gap(glo[2], ghi[2], lo[2], hi[2]), gub, mset);
+}
+
+// ---------------------------------------------------------------------------------------------
 // 3x3 SVD by one-sided (Hestenes) Jacobi, register resident.  H = U diag(S) V^T, S sorted
 // descending like torch.svd (model_utils.py:233).
 // ---------------------------------------------------------------------------------------------

@@ -357,11 +357,30 @@ __device__ __forceinline__ void take_units(float ta, float tb, int unit0, float&
 // MSET (a compile-time superset of `need`; walk_variant, houv_math.h): a metric outside it has no remembered-neighbour distance, no
 // box distance, no compare and no OR.  Its verdict was "no box passes" before (bound -1 against a distance >= 0 or NaN), so the
 // masks are the same bits.  A metric inside MSET but outside `need` keeps the run-time bound -1.
-template <int BLOCK, int Q, int NMET, int MSET = (1 << NMET) - 1>
+//
+// Group cull (box_test_group, houv_math.h, where the proof is): a wave's 64 queries of one k are 64 consecutive points of a
+// k-d-sorted cloud -- two leaves (one super-tile under TS = 1), whose boxes tile_boxes has already formed from the very
+// coordinates tested here (`qboxes`; entries past `nqtile` were never written and are left out).  Per k, lane b tests reference
+// box b against that group box with the wave's largest bound per metric; the ballot is the 64-bit scalar mask of the boxes that
+// ANY query of the group can pass, and the per-query tests run in a scalar loop over its set bits only.  A culled box fails
+// every lane's own test, so the visit masks are the bits the full loop over all boxes gave, not a superset.
+// `qboxes` of sweep A is sm.mbox, written before the call with no barrier in between: a wave reads only the (up to) two entries
+// of its own lanes 0 and 32 for each k, and a wave's LDS accesses complete in order.
+// Out: the masks, parked in the .w lanes of wlo / whi at the queries' own indices (low / high word), and their lengths `len`.
+// nsurv_out: the boxes that survived, summed over the wave's Q groups (a scalar; pruned_sweep_sorted counts it).
+__device__ __forceinline__ unsigned& w_slot(float4* cloud, int q) { return reinterpret_cast<unsigned*>(cloud + q)[3]; }
+__device__ __forceinline__ unsigned lane_bit(unsigned long long lanes) {   // 1 in the lanes of a compare's SGPR pair, else 0
+  unsigned r;
+  asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(lanes));
+  return r;
+}
+
+template <int BLOCK, int Q, int NMET, int MSET = (1 << NMET) - 1, int TS = 0>
 __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
+                                            const float4* qboxes, int nqtile,
                                             const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
                                             buf_t ws, int prev_off, int count, unsigned need,
-                                            unsigned long long (&un)[Q]) {
+                                            float4* wlo, float4* whi, int (&len)[Q], int& nsurv_out) {
   float ub[Q][NMET];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
@@ -387,47 +406,97 @@ __device__ __forceinline__ void prune_masks(const float4* __restrict__ refs, con
     for (int m = 0; m < NMET; ++m)   // box distances are rounded: stay conservative
       if ((MSET >> m) & 1) ub[k][m] = (ok && ((need >> m) & 1u)) ? (ub[k][m] * 1.00001f + 1e-30f) : -1.f;
   }
+  // ---- group verdicts: lane b holds reference box b ----
+  unsigned long long surv[Q];
+  {
+    const int bl = tid_x() & 63;
+    const bool live = bl < ntile;
+    const float4 blo4 = boxes[live ? 2 * bl : 0], bhi4 = boxes[live ? 2 * bl + 1 : 1];
+    const float blo[3] = {blo4.x, blo4.y, blo4.z}, bhi[3] = {bhi4.x, bhi4.y, bhi4.z};
+    const int wave0 = __builtin_amdgcn_readfirstlane(tid_x()) & ~63;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+      float gub[NMET];
+#pragma unroll
+      for (int m = 0; m < NMET; ++m) {
+        gub[m] = -1.f;
+        if ((MSET >> m) & 1) gub[m] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_fmax_to_lane63(ub[k][m])), 63));
+      }
+      float glo[3] = {INFINITY, INFINITY, INFINITY}, ghi[3] = {-INFINITY, -INFINITY, -INFINITY};
+      const int t0 = (pt_base<BLOCK>(k) + wave0) >> (5 + TS);
+#pragma unroll
+      for (int h = 0; h < 2 - TS; ++h) {
+        if (t0 + h < nqtile) {   // wave-uniform
+          const float4 l = qboxes[2 * (t0 + h)], u = qboxes[2 * (t0 + h) + 1];
+          glo[0] = fminf(glo[0], l.x); glo[1] = fminf(glo[1], l.y); glo[2] = fminf(glo[2], l.z);
+          ghi[0] = fmaxf(ghi[0], u.x); ghi[1] = fmaxf(ghi[1], u.y); ghi[2] = fmaxf(ghi[2], u.z);
+        }
+      }
+      surv[k] = __builtin_amdgcn_ballot_w64(live && box_test_group<NMET>(glo, ghi, blo, bhi, gub, (unsigned)MSET));
+    }
+  }
   unsigned alo[Q], ahi[Q];
 #pragma unroll
   for (int k = 0; k < Q; ++k) alo[k] = ahi[k] = 0u;
-  // per query and box (17 instructions; wave-uniform t: the box reads are LDS broadcasts): the box point nearest to the query is
-  // the query clamped into the box (v_med3), its offset squared per axis and summed per metric; the verdicts are collected
-  // one bit per box by shift_in, so the boxes run in DESCENDING order, 32 per mask word
-  auto test = [&](const float4 lo, const float4 hi, unsigned (&acc)[Q]) {
-#pragma unroll
-    for (int k = 0; k < Q; ++k) {
-      const float dx = qx[k] - __builtin_amdgcn_fmed3f(qx[k], lo.x, hi.x);
-      const float dy = qy[k] - __builtin_amdgcn_fmed3f(qy[k], lo.y, hi.y);
-      const float dz = qz[k] - __builtin_amdgcn_fmed3f(qz[k], lo.z, hi.z);
-      unsigned long long in;                              // lane mask of the compares, OR-ed on the scalar unit (no branches)
-      if constexpr (NMET == 4) {
-        const float xx = dx * dx, yy = dy * dy;
-        const float s3 = __builtin_fmaf(dy, dy, xx), s1 = __builtin_fmaf(dz, dz, yy), s2 = __builtin_fmaf(dz, dz, xx);
-        const float s0 = __builtin_fmaf(dz, dz, s3);
-        in = 0ull;                                        // s3 is still formed where s0 needs it
-        if constexpr ((MSET & 1) != 0) in |= __builtin_amdgcn_ballot_w64(s0 <= ub[k][0]);
-        if constexpr ((MSET & 2) != 0) in |= __builtin_amdgcn_ballot_w64(s1 <= ub[k][1]);
-        if constexpr ((MSET & 4) != 0) in |= __builtin_amdgcn_ballot_w64(s2 <= ub[k][2]);
-        if constexpr ((MSET & 8) != 0) in |= __builtin_amdgcn_ballot_w64(s3 <= ub[k][3]);
-      } else {
-        in = __builtin_amdgcn_ballot_w64(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) <= ub[k][0]);
-      }
-      acc[k] = shift_in_mask(acc[k], in);
+  // per query and surviving box (18 instructions; wave-uniform box: the reads are LDS broadcasts from a scalar address): the box
+  // point nearest to the query is the query clamped into the box (v_med3), its offset squared per axis and summed per metric; the
+  // verdict goes to bit `bit` of the word: the lane's 0 / 1 of the OR-ed compares, shifted and OR-ed in one instruction
+  auto test = [&](const float4 lo, const float4 hi, int k, int bit, unsigned& acc) {
+    const float dx = qx[k] - __builtin_amdgcn_fmed3f(qx[k], lo.x, hi.x);
+    const float dy = qy[k] - __builtin_amdgcn_fmed3f(qy[k], lo.y, hi.y);
+    const float dz = qz[k] - __builtin_amdgcn_fmed3f(qz[k], lo.z, hi.z);
+    unsigned long long in;                              // lane mask of the compares, OR-ed on the scalar unit (no branches)
+    if constexpr (NMET == 4) {
+      const float xx = dx * dx, yy = dy * dy;
+      const float s3 = __builtin_fmaf(dy, dy, xx), s1 = __builtin_fmaf(dz, dz, yy), s2 = __builtin_fmaf(dz, dz, xx);
+      const float s0 = __builtin_fmaf(dz, dz, s3);
+      in = 0ull;                                        // s3 is still formed where s0 needs it
+      if constexpr ((MSET & 1) != 0) in |= __builtin_amdgcn_ballot_w64(s0 <= ub[k][0]);
+      if constexpr ((MSET & 2) != 0) in |= __builtin_amdgcn_ballot_w64(s1 <= ub[k][1]);
+      if constexpr ((MSET & 4) != 0) in |= __builtin_amdgcn_ballot_w64(s2 <= ub[k][2]);
+      if constexpr ((MSET & 8) != 0) in |= __builtin_amdgcn_ballot_w64(s3 <= ub[k][3]);
+    } else {
+      in = __builtin_amdgcn_ballot_w64(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)) <= ub[k][0]);
+    }
+    acc |= lane_bit(in) << bit;
+  };
+  // the set bits of one word of a survivor mask, lowest first (any order would do), scanned on the scalar unit.  The next
+  // survivor's box is read while this one is tested (after the last one, that box again: a read for nothing): the reads are
+  // issued ahead of the test -- the scheduler moves nothing across the barrier; left alone it sinks them below the test and the
+  // loop waits out an LDS round trip per box -- and are first needed, by an empty asm, before the back-edge.  Whole float4s:
+  // ds_read_b128 takes half the LDS cycles of ds_read_b96.
+  auto run = [&](unsigned w, int t_base, int k, unsigned& acc) {
+    if (w == 0u) return;
+    int b = __builtin_ctz(w);
+    float4 lo = boxes[2 * (t_base + b)], hi = boxes[2 * (t_base + b) + 1];
+    for (;;) {
+      w &= w - 1u;
+      asm volatile("" : "+s"(w));
+      const int nb = w != 0u ? __builtin_ctz(w) : b;
+      const float4 nlo = boxes[2 * (t_base + nb)], nhi = boxes[2 * (t_base + nb) + 1];
+      __builtin_amdgcn_sched_barrier(0);
+      test(lo, hi, k, b, acc);
+      asm volatile("" ::"v"(nlo.x), "v"(nlo.y), "v"(nlo.z), "v"(nlo.w), "v"(nhi.x), "v"(nhi.y), "v"(nhi.z), "v"(nhi.w));
+      if (w == 0u) break;
+      b = nb; lo = nlo; hi = nhi;
     }
   };
-  auto run = [&](int t_first, int t_last, unsigned (&acc)[Q]) {      // t_first >= t_last; the next box is in flight while this one is tested
-    float4 lo = boxes[2 * t_first], hi = boxes[2 * t_first + 1];
-    for (int t = t_first; t >= t_last; --t) {
-      const int tn = t > 0 ? t - 1 : 0;
-      const float4 nlo = boxes[2 * tn], nhi = boxes[2 * tn + 1];
-      test(lo, hi, acc);
-      lo = nlo; hi = nhi;
-    }
-  };
-  if (ntile > 32) run(ntile - 1, 32, ahi);
-  run((ntile < 32 ? ntile : 32) - 1, 0, alo);
+  int nsurv = 0;
 #pragma unroll
-  for (int k = 0; k < Q; ++k) un[k] = ((unsigned long long)ahi[k] << 32) | alo[k];
+  for (int k = 0; k < Q; ++k) {
+    run((unsigned)surv[k], 0, k, alo[k]);
+    run((unsigned)(surv[k] >> 32), 32, k, ahi[k]);
+    nsurv += __popcll(surv[k]);
+    // the mask is parked here, in the .w lanes of the two clouds (see pruned_sweep_sorted), inside the code of the metric set:
+    // its length alone leaves, not eight mask registers that meet those of the other sets' copies
+    len[k] = __popc(alo[k]) + __popc(ahi[k]);
+    const int q = pt_index<BLOCK>(k);
+    if (q < count) {
+      w_slot(wlo, q) = alo[k];
+      w_slot(whi, q) = ahi[k];
+    }
+  }
+  nsurv_out = nsurv;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -452,7 +521,6 @@ struct SortedStage {
   int* hist;                  // [65 + 65 + 2]  bin counts (by 64 - length) | bin bases | next block
 };
 
-__device__ __forceinline__ unsigned& w_slot(float4* cloud, int q) { return reinterpret_cast<unsigned*>(cloud + q)[3]; }
 
 // wlo / whi: the two LDS clouds (both hold >= count entries); .w of wlo[q] carries the low half of query q's mask and,
 // after the walk, the tracking-unit ids (8 bits each: <= 256 units of 16 references) of its minima; .w of whi[q] the high half.
@@ -465,6 +533,9 @@ __device__ __forceinline__ unsigned& w_slot(float4* cloud, int q) { return reint
 // switch each -- box tests and a block loop compiled for the metric set MSET.  The counting sort and the barriers S1..S3 between
 // the two are common code: every wave meets the same barriers whichever variant it runs.
 // `walk_hist` (houv_debug_set("solve_walk_hist")): 16 counters, +1 in slot `need` per wave and sweep; null = off.
+// `qboxes`: the boxes of the QUERY cloud (the other of sm.tbox / sm.mbox), see prune_masks.
+// `cull` (houv_debug_set("solve_cull_stats")): four counters, added to once per wave and sweep -- groups tested (Q), boxes
+// surviving, per-query tests executed, per-query tests of a loop over all boxes (the last two per lane: 64 a box); null = off.
 template <typename F>
 __device__ __forceinline__ void walk_dispatch(unsigned mset, F&& f) {
 #define HOUV_WALK_CASE(S)                                                          \
@@ -481,33 +552,31 @@ __device__ __forceinline__ void walk_dispatch(unsigned mset, F&& f) {
 
 template <int BLOCK, int Q, int NMET, int TS = 0>
 __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ refs, const float4* __restrict__ boxes, int ntile,
-                                                    const float4* __restrict__ qarr, float4* wlo, float4* whi,
+                                                    const float4* qboxes, const float4* __restrict__ qarr, float4* wlo, float4* whi,
                                                     const float (&qx)[Q], const float (&qy)[Q], const float (&qz)[Q],
                                                     buf_t ws, int prev_off, int count, unsigned need,
                                                     const SortedStage& st, float4* __restrict__ res, float (&best)[Q][NMET],
                                                     int (&btile)[Q][NMET], unsigned long long* __restrict__ stats,
-                                                    unsigned long long* __restrict__ walk_hist) {
+                                                    unsigned long long* __restrict__ walk_hist,
+                                                    unsigned long long* __restrict__ cull) {
   static_assert(BLOCK % 64 == 0 && BLOCK >= 128, "whole waves; thread 64 resets the block counter");
   const int tid = tid_x(), lane = tid & 63;
-  unsigned long long un[Q];
+  const int nqtile = (count + (kSub << TS) - 1) >> (5 + TS);   // boxes of the query cloud that tile_boxes wrote
+  int len[Q], rnk[Q];
+  int nsurv = 0;
   if constexpr (NMET == 4) {
     walk_dispatch((unsigned)(walk_variant_table() >> (4u * need)) & 15u, [&](auto mset) {
-      prune_masks<BLOCK, Q, NMET, decltype(mset)::value>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, need, un);
+      prune_masks<BLOCK, Q, NMET, decltype(mset)::value, TS>(refs, boxes, ntile, qboxes, nqtile, qx, qy, qz, ws, prev_off, count, need,
+                                                             wlo, whi, len, nsurv);
     });
   } else {
-    prune_masks<BLOCK, Q, NMET>(refs, boxes, ntile, qx, qy, qz, ws, prev_off, count, need, un);
+    prune_masks<BLOCK, Q, NMET, 1, TS>(refs, boxes, ntile, qboxes, nqtile, qx, qy, qz, ws, prev_off, count, need, wlo, whi,
+                                       len, nsurv);
   }
-  int len[Q], rnk[Q];
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
-    const int q = pt_index<BLOCK>(k);
-    len[k] = __popcll(un[k]);
     rnk[k] = 0;
-    if (q < count) {
-      w_slot(wlo, q) = (unsigned)un[k];
-      w_slot(whi, q) = (unsigned)(un[k] >> 32);
-      rnk[k] = atomicAdd(&st.hist[64 - len[k]], 1);        // place inside its bin (any order: results do not depend on it)
-    }
+    if (pt_index<BLOCK>(k) < count) rnk[k] = atomicAdd(&st.hist[64 - len[k]], 1);   // place inside its bin (any order: results do not depend on it)
   }
   // barrier S1 -- writers: every thread's bin atomics above; readers: every wave's bin scan below.  It also orders the previous
   // walk's last block-counter atomics (all before barrier S3 of that sweep) against the counter's reset here.
@@ -588,6 +657,14 @@ __device__ __forceinline__ void pruned_sweep_sorted(const float4* __restrict__ r
   if constexpr (NMET == 4) walk_dispatch((unsigned)(walk_variant_table() >> (4u * need)) & 15u, walk_blocks);
   else walk_blocks(std::integral_constant<int, 1>{});
   if (walk_hist && lane == 0) atomicAdd(&walk_hist[need & 15u], 1ull);   // the unit of stats[2]
+  if (cull && lane == 0) {
+    nsurv = __builtin_amdgcn_readfirstlane(nsurv);
+    asm volatile("" : "+s"(ntile));   // the product below is formed here, not kept in registers around the iteration loop
+    atomicAdd(&cull[0], (unsigned long long)Q);
+    atomicAdd(&cull[1], (unsigned long long)nsurv);
+    atomicAdd(&cull[2], 64ull * (unsigned long long)nsurv);
+    atomicAdd(&cull[3], 64ull * (unsigned long long)(Q * ntile));
+  }
   if (stats) {
     asked = wave_incl_scan_dpp(asked);
     if (lane == 63) atomicAdd(&stats[0], (unsigned long long)asked);

@@ -49,6 +49,9 @@ struct SolveArgs : SolveCommon {
                                // [6] Chamfer terms computed and [7] terms possible (2 x metrics), per workgroup-iteration
   unsigned long long* walk_hist;   // houv_debug_set("solve_walk_hist", device pointer): 16 counters, slot = the term mask `need` of a
                                    // pruned sweep, +1 per walking wave (the unit of stats[2]); read where it is used only (fresh)
+  unsigned long long* cull_stats;  // houv_debug_set("solve_cull_stats", device pointer): 4 counters of the box tests' group cull
+                                   // (prune_masks): groups tested, boxes surviving, per-query tests executed, per-query tests of a
+                                   // loop over all boxes; read where it is used only (fresh)
 };
 
 constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS reads (recover_nn)
@@ -86,7 +89,8 @@ constexpr int kTermAges = 8;      // sm.anchor[kTermAges] as unsigned: 8 bits pe
 // Records of the term masks (term_anchor_masks, houv_math.h).  A term computed in the iteration that just ended has that
 // iteration's pose as its record pose: it is still in sm.pose when the rule runs.  At most one term per metric is older (it was
 // dropped): its record pose, 12 floats per metric, lives in the .w lanes of sm.tbox -- tile_boxes writes .w = 0 there once per
-// launch in the prologue, prune_masks reads x, y, z of a box only, and sm.tbox has 128 entries whatever the cloud size.
+// launch in the prologue, prune_masks uses x, y, z of a box only (its read-ahead loads the whole float4), and sm.tbox has 128
+// entries whatever the cloud size.
 constexpr int kStalePose = 4;     // floats between two consecutive entries of a stale pose (one float4 of sm.tbox each)
 
 
@@ -543,14 +547,15 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       float best[Q][NMET];
       int btile[Q][NMET];
       if constexpr (PRUNE) {
-        tile_boxes<BLOCK, Q, TS>(mx, my, mz, N, npad / kPad, sm.mbox);   // read by sweep B after the next barriers
+        tile_boxes<BLOCK, Q, TS>(mx, my, mz, N, npad / kPad, sm.mbox);   // read by sweep B after the next barriers, and by sweep A's
+                                                                         // group cull: each wave its own lanes' entries
         pruned_now = (a.ws_valid != 0) || (it > 0);
       }
       if (need_a != 0u) {   // none of A's terms needed: no walk, no selection, no sums (the move and the boxes above are for sweep B)
         if (pruned_now) {
           if constexpr (PRUNE != 0)
-            pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
-                                                need_a, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist));
+            pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.tgt, sm.tbox, mpad / kPad, sm.mbox, sm.mov, sm.tgt, sm.mov, mx, my, mz, ws, ws_a, N,
+                                                need_a, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist), fresh(a.cull_stats));
         } else {
           sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
           if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
@@ -592,8 +597,8 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         int btile[Q][NMET];
         if (pruned_now) {
           if constexpr (PRUNE != 0)
-            pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
-                                                need_b, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist));
+            pruned_sweep_sorted<BLOCK, Q, NMET, TS>(sm.mov, sm.mbox, npad / kPad, sm.tbox, sm.tgt, sm.tgt, sm.mov, tx, ty, tz, ws, ws_b, M,
+                                                need_b, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist), fresh(a.cull_stats));
         } else {
           sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
           if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
@@ -829,7 +834,8 @@ static int solve_dispatch(const houv::SolveCommon& c, int use_views, short* nn_w
   // pred_mode / stats are diagnostics set through houv_debug_set(), never through the environment.
   SolveArgs a{c, nn_ws, ws_valid, ws_stride, g_debug.pred_mode.load(),
               reinterpret_cast<unsigned long long*>(g_debug.stats.load()),
-              reinterpret_cast<unsigned long long*>(g_debug.walk_hist.load())};
+              reinterpret_cast<unsigned long long*>(g_debug.walk_hist.load()),
+              reinterpret_cast<unsigned long long*>(g_debug.cull_stats.load())};
   hipStream_t s = (hipStream_t)stream;
   const int mx = N > M ? N : M;
   int block = 0, q = 0, mode = 0;

@@ -166,7 +166,9 @@ long long houv_solve_lds_bytes(int N, int M, int pruned);
 /* The pruned four-metric kernels compile their box tests and their walk for a few metric sets only.  `need` (0..15, bit m = this
  * direction's Chamfer term of metric m is computed in this iteration) runs on the returned set: a superset of `need`, 15 = all
  * four metrics (host-only query, no GPU work; -1 with houv_last_error() set for a mask outside 0..15).  Results do not depend on
- * the table.  houv_debug_set("solve_walk_hist", address of 16 uint64 on the device) counts the masks the walks see.
+ * the table.  houv_debug_set("solve_walk_hist", address of 16 uint64 on the device) counts the masks the walks see;
+ * houv_debug_set("solve_cull_stats", address of 4 uint64 on the device) counts what the group cull of the box tests did: groups
+ * tested, boxes surviving, per-query tests executed, per-query tests of a loop over all boxes.
  * No counterpart in the reference; exported so that the test-suite can prove that every compiled set is exercised. */
 int houv_solve_walk_variant(int need);
 
