@@ -70,6 +70,8 @@ _SIGNATURES = {
     "houv_mlp2_max": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, ctypes.c_longlong, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
     "houv_mlp2_max_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
     "houv_pcn_fold": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "houv_knn_feat": (ctypes.c_int, [_c_f, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
+    "houv_dense_conv": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 6 + [_int, _c_f, _int, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

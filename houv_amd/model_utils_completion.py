@@ -5,10 +5,13 @@ loop itself never calls them -- it runs inside houv_solve_iterate.
 Below them, the sampling / regularisation helpers of the same file that sit on the mm3d_pn2 point ops
 (edge_preserve_sampling :178-204, get_repulsion_loss :278-297, get_uniform_loss :300-330, knn :346-351, knn_point :354-365,
 symmetric_sample :383-392, three_nn_upsampling :395-402), with the reference's signatures and return tuples, and the folding
-grids of the completion decoders (gen_grid :223-227, gen_1d_grid :230-233, gen_grid_up :236-249; pure torch, on the CPU)."""
+grids of the completion decoders (gen_grid :223-227, gen_1d_grid :230-233, gen_grid_up :236-249; pure torch, on the CPU).
+From completion/model_utils.py, for the ECG network (houv_amd/models/ecg.py): knn on features of up
+to 256 channels (houv_knn_feat), get_graph_feature :164-187, get_edge_features :119-132 and EF_expansion :24-55."""
 import math
 
 import torch
+import torch.nn as nn
 
 from . import _lib, ops
 from .metrics import cd, emd
@@ -95,12 +98,16 @@ def knn_point(pk, point_input, point_output):
 
 
 def knn(x, k):
-    """x (B,3,N) -> (B,N,k) int64 indices of each point's k nearest points, itself first.  houv_knn serves k = 1, 3, 8, 16, 20;
-    any other k <= 32 goes through houv_knn_cross of the cloud with itself."""
+    """x (B,C,N) -> (B,N,k) int64 indices of each point's k nearest points, itself first.  C = 3: houv_knn serves k = 1, 3, 8, 16,
+    20; any other k <= 32 goes through houv_knn_cross of the cloud with itself.  Any other C <= 256 (features): houv_knn_feat,
+    which ranks the direct form d = fma(t, t, d), t = x_j[c] - x_i[c], c ascending, the lower index first among equal distances;
+    the reference ranks the expanded form -|a|^2 + 2ab - |b|^2 with torch.topk and differs at near-ties."""
     _lib.require_gpu(x)
-    if x.dim() != 3 or x.shape[1] != 3:
-        raise _lib.HouvHipError("knn: expected x[B,3,N] (only 3-D coordinates have a kernel)")
+    if x.dim() != 3 or not 1 <= x.shape[1] <= 256:
+        raise _lib.HouvHipError("knn: expected x[B,C,N] with 1 <= C <= 256")
     pts = x.detach().transpose(1, 2).contiguous().float()
+    if x.shape[1] != 3:
+        return ops.knn_feat(pts, k).long()
     if k in (1, 3, 8, 16, 20) and k <= pts.shape[1]:
         return ops.knn(pts, k).long()
     return knn_cross(k, pts, pts)[1].long()
@@ -176,3 +183,86 @@ def three_nn_upsampling(target_points, source_points):
     dist, idx = three_nn(target_points, source_points)
     inv = 1.0 / dist.clamp_min(1e-10)
     return idx, inv / inv.sum(dim=2, keepdim=True)
+
+
+def _take_rows(rows, idx):
+    """rows (B,N,C) (any row stride), idx (B,...) -> (B,...,C) = rows[b, idx[b,...]]."""
+    B, _, C = rows.shape
+    flat = idx.reshape(B, -1, 1).long().expand(-1, -1, C)
+    return torch.gather(rows, 1, flat).view(*idx.shape, C)
+
+
+def get_edge_features(x, idx):
+    """x (B,C,1,N) or (B,C,N), idx (B,N,k) -> (B,C,k,N): the features of every point's listed neighbours (model_utils.py:119-132)."""
+    if x.dim() == 4:
+        x = x.squeeze(2)
+    return _take_rows(x.transpose(1, 2), idx).permute(0, 3, 2, 1)
+
+
+def get_graph_feature(x, k=20, minus_center=True, idx=None):
+    """x (B,C,N) -> (B,2C,N,k): cat(x_i, x_j - x_i) (minus_center) or cat(x_i, x_j) over each point's k nearest points in feature
+    space, itself first (model_utils.py:164-187).  This is the reference's materialised layout, for callers that want it;
+    Dense_conv does not build it (houv_dense_conv).  `idx` (B,N,k), when given, replaces the search."""
+    if idx is None:
+        idx = knn(x, k)
+    rows = x.transpose(1, 2)
+    feature = _take_rows(rows, idx)                                               # (B,N,k,C)
+    centre = rows.unsqueeze(2).expand_as(feature)
+    return torch.cat((centre, feature - centre if minus_center else feature), dim=3).permute(0, 3, 1, 2)
+
+
+class Conv1x1(nn.Module):
+    """Parameter holder with the names, shapes and default initialisation of nn.Conv1d (dims = 1: weight [out, in, 1]) or
+    nn.Conv2d (dims = 2: [out, in, 1, 1]) for a kernel of size 1: the product itself runs on houv_gemm_f32 or inside a fused
+    kernel."""
+
+    def __init__(self, n_in, n_out, dims=1):
+        super().__init__()
+        bound = 1 / math.sqrt(n_in)
+        self.weight = nn.Parameter(torch.empty((n_out, n_in) + (1,) * dims).uniform_(-bound, bound))
+        self.bias = nn.Parameter(torch.empty(n_out).uniform_(-bound, bound))
+
+    def matrix(self):
+        return self.weight.view(self.weight.shape[0], self.weight.shape[1])
+
+    def rows(self, x, relu=False, out=None, lo=0, hi=None):
+        """x (..., hi - lo) rows (one row stride) -> relu?(x . matrix()[:, lo:hi]^T + bias), written to `out` when given."""
+        W = self.matrix()[:, lo:hi]
+        y = ops.gemm(x.reshape(-1, x.shape[-1]) if x.is_contiguous() else x.view(-1, x.shape[-1]), W,
+                     None if out is None else out.view(-1, out.shape[-1]), shift=self.bias, relu=relu)
+        return y.view(*x.shape[:-1], W.shape[0]) if out is None else out
+
+
+class EF_expansion(nn.Module):
+    """model_utils.py:24-55: x (B,input_size,N) -> (B,output_size,N*step_ratio), composed from houv_knn_feat, row gathers and
+    houv_gemm_f32 (not fused: ECG uses it only when num_points > num_coarse + num_input).  The reference's view / permute chain
+    is kept: the (B,k,N,output_size*step_ratio) activations of conv2 are REINTERPRETED as (B,k,N*step_ratio,output_size)."""
+
+    def __init__(self, input_size, output_size=64, step_ratio=2, k=4):
+        super().__init__()
+        self.step_ratio, self.k, self.input_size, self.output_size = step_ratio, k, input_size, output_size
+        self.conv1 = Conv1x1(input_size * 2, output_size, 2)
+        self.conv2 = Conv1x1(input_size * 2 + output_size, output_size * step_ratio, 2)
+        self.conv3 = Conv1x1(output_size, output_size, 2)
+
+    @torch.no_grad()
+    def forward_rows(self, rows, idx=None, trace=None):
+        """rows (B,N,input_size) -> (B,N*step_ratio,output_size)."""
+        B, N, C = rows.shape
+        if idx is None:
+            idx = ops.knn_feat(rows, self.k)
+        if trace is not None:
+            trace["knn_exp"], trace["knn_exp_x"] = idx, rows.clone()
+        k = idx.shape[2]
+        nb = _take_rows(rows, idx).permute(0, 2, 1, 3)                            # (B,k,N,C): the reference's B C K N as rows
+        edge = torch.cat((rows.unsqueeze(1).expand_as(nb), nb), dim=3).contiguous()
+        cat = torch.empty((B, k, N, self.output_size + 2 * C), dtype=rows.dtype, device=rows.device)
+        cat[..., :self.output_size] = self.conv1.rows(edge)
+        cat[..., self.output_size:] = edge
+        e = self.conv2.rows(torch.relu_(cat), relu=True)                          # (B,k,N,output_size*step_ratio)
+        e = self.conv3.rows(e.view(B, k, N * self.step_ratio, self.output_size))
+        return e.amax(dim=1)
+
+    @torch.no_grad()
+    def forward(self, x):
+        return self.forward_rows(x.transpose(1, 2).contiguous().float()).transpose(1, 2).contiguous()

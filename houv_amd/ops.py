@@ -450,6 +450,64 @@ def pcn_fold(coarse, cvec, grid, Wgp, W2, b2, W3, b3):
 
 
 # ---------------------------------------------------------------------------------------------------
+# ECG completion network (houv_knn_feat, houv_dense_conv)
+# ---------------------------------------------------------------------------------------------------
+KNN_FEAT_BLOCK, KNN_FEAT_CHUNK = 32, 16   # HOUV_KNN_FEAT_BLOCK / _CHUNK: candidates per register block, channels per chunk
+DENSE_CONV_GROWTH = 24                     # HOUV_DENSE_CONV_GROWTH
+
+
+def _rows(t, name):
+    """(B, N, C, row stride) of a [B,N,C] view whose rows are contiguous and evenly spaced over the whole batch (a column slice
+    of one row-major buffer qualifies)."""
+    if t.dim() != 3 or t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) < t.shape[2]:
+        raise _lib.HouvHipError(f"{name}: expected [B,N,C] rows with unit channel stride and one row stride, got shape "
+                                f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    return t.shape[0], t.shape[1], t.shape[2], t.stride(1)
+
+
+def knn_feat(x, k, want_dist=False):
+    """x[B,N,C] feature rows (C <= 256; a column slice of a wider row-major buffer is fine) -> idx[B,N,k] int32, nearest first,
+    the point itself included, ranked by the fp32 chain d = fma(t, t, d), t = x[j,c] - x[i,c], c ascending, the lower index
+    first among equal d (houv_knn_feat).  want_dist: (idx, dist2[B,N,k])."""
+    _lib.require_gpu_any(x)
+    B, N, C, ldx = _rows(x, "knn_feat: x")
+    idx = torch.empty((B, N, int(k)), dtype=_I32, device=x.device)
+    d2 = torch.empty((B, N, int(k)), dtype=_F32, device=x.device) if want_dist else None
+    with torch.cuda.device(x.device):
+        ok = _lib.load().houv_knn_feat(ctypes_ptr(x), B, N, C, ldx, int(k), _lib.ptr(idx), _lib.ptr(d2), _lib.stream_of(x))
+    _lib.check(ok, "houv_knn_feat")
+    return (idx, d2) if want_dist else idx
+
+
+def dense_conv(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
+    """Dense_conv.forward (completion/models/ecg.py:58-65; growth rate 24, dense_n 3) in one kernel (houv_dense_conv): x[B,N,C]
+    rows (C = 24 or 48), idx[B,N,k] int32 neighbour lists, W0[24,2C], W1[24,24+C], W2[24,48+C], biases [24] ->
+    out[B,N,C+72] = max over the neighbours of cat(y0, x_i, s1, s2), relu applied when relu_out.  `out` may be a [B,N,C+72]
+    column slice of a wider row-major buffer (the caller's cat(dense, x)); its other columns are left alone."""
+    _lib.require_gpu_any(x, W0, b0, W1, b1, W2, b2, out)
+    _lib.require_gpu(idx, W0, b0, W1, b1, W2, b2); _want(idx, _I32, "dense_conv: idx")
+    B, N, C, ldx = _rows(x, "dense_conv: x")
+    G = DENSE_CONV_GROWTH
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.HouvHipError(f"dense_conv: expected idx[{B},{N},k], got {tuple(idx.shape)}")
+    if tuple(W0.shape) != (G, 2 * C) or tuple(W1.shape) != (G, G + C) or tuple(W2.shape) != (G, 2 * G + C) \
+            or b0.numel() != G or b1.numel() != G or b2.numel() != G:
+        raise _lib.HouvHipError(f"dense_conv: expected W0[24,{2 * C}], W1[24,{G + C}], W2[24,{2 * G + C}] and biases [24], got "
+                                f"{tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    if out is None:
+        out = torch.empty((B, N, C + 3 * G), dtype=_F32, device=x.device)
+    if tuple(out.shape) != (B, N, C + 3 * G):
+        raise _lib.HouvHipError(f"dense_conv: out must be [{B},{N},{C + 3 * G}], got {tuple(out.shape)}")
+    ldo = _rows(out, "dense_conv: out")[3]
+    with torch.cuda.device(x.device):
+        ok = _lib.load().houv_dense_conv(ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, idx.shape[2], _lib.ptr(W0), _lib.ptr(b0),
+                                         _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), int(bool(relu_out)),
+                                         ctypes_ptr(out), ldo, _lib.stream_of(x))
+    _lib.check(ok, "houv_dense_conv")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------
 _registered = False
@@ -487,6 +545,9 @@ def register_torch_ops():
     lib.define("edge_diff(Tensor x, Tensor idx, int k, int ldo) -> Tensor")
     lib.define("mlp2_max(Tensor x, Tensor W1, Tensor shift1, Tensor W2, Tensor b2) -> (Tensor, Tensor)")
     lib.define("pcn_fold(Tensor coarse, Tensor cvec, Tensor grid, Tensor Wgp, Tensor W2, Tensor b2, Tensor W3, Tensor b3) -> Tensor")
+    lib.define("knn_feat(Tensor x, int k) -> (Tensor, Tensor)")
+    lib.define("dense_conv(Tensor x, Tensor idx, Tensor W0, Tensor b0, Tensor W1, Tensor b1, Tensor W2, Tensor b2, "
+               "bool relu_out) -> Tensor")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
     lib.impl("kabsch", kabsch, "CUDA")
@@ -522,6 +583,11 @@ def register_torch_ops():
         return mlp2_max(*a, want_y=True)
     lib.impl("mlp2_max", _mlp2_max, "CUDA")
     lib.impl("pcn_fold", pcn_fold, "CUDA")
+
+    def _knn_feat(x, k):
+        return knn_feat(x, k, want_dist=True)
+    lib.impl("knn_feat", _knn_feat, "CUDA")
+    lib.impl("dense_conv", dense_conv, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

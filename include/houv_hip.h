@@ -436,6 +436,44 @@ long long houv_mlp2_max_workspace_bytes(int B, int N, int Cout);
 int houv_pcn_fold(const float* coarse, const float* cvec, const float* grid, int B, int nc, int scale, const float* Wgp,
                   const float* W2, const float* b2, const float* W3, const float* b3, float* fine, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ECG completion network (completion/models/ecg.py).  fp32 data, fixed expression trees, no allocation,
+ * no atomics, no scratch: results are bit-identical from call to call.  Each returns 0 with houv_last_error() set, launching
+ * nothing, when a check fails (a NULL pointer included). */
+
+/* Candidates per register block and channels per chunk of houv_knn_feat: the sizes at whose edges a partial block begins. */
+#define HOUV_KNN_FEAT_BLOCK 32
+#define HOUV_KNN_FEAT_CHUNK 16
+/* Growth rate of houv_dense_conv (the G of ecg.py's Dense_conv as ECG builds it). */
+#define HOUV_DENSE_CONV_GROWTH 24
+
+/* k nearest neighbours in feature space (get_graph_feature's knn, completion/model_utils.py).  x[B,N,C] token-major rows of
+ * stride ldx >= C floats; idx[B,N,k] and dist2_or_null[B,N,k] nearest first; the point itself is a candidate.
+ * 1 <= C <= 256, 1 <= k <= 32, k <= N <= 16384, B <= 65535 (B = 0 launches nothing).
+ * The ranked value is, in fp32:   d = 0;  for c = 0 .. C-1:  t = x[j,c] - x[i,c];  d = fmaf(t, t, d)
+ * and equal d puts the lower index first (the stable insertion of houv_knn_cross).  With C = 3 this is houv_knn_cross(x, x)'s
+ * value bit for bit.  The chain is order-defined, so a host function reproduces idx AND dist2 exactly.
+ * The reference ranks the expanded form -|a|^2 + 2ab - |b|^2 in fp32 with torch.topk, which cancels where two rows are close:
+ * it differs from this (and from itself in float64) at near-ties, 17-112 of the 16384 entries of a 1024 x 16 list measured on
+ * its own activations.  The [B,N,N] matrix it builds does not exist here. */
+int houv_knn_feat(const float* x, int B, int N, int C, int ldx, int k, int32_t* idx, float* dist2_or_null, void* stream);
+
+/* Dense_conv.forward (ecg.py:58-65) with growth rate G = 24 and dense_n = 3, fused through the maximum over the neighbours.
+ * x[B,N,C] rows of stride ldx >= C; idx[B,N,k] neighbour lists into the SAME cloud (an entry outside 0..N-1 is clamped into
+ * that range: nothing outside x is read); W0[G,2C], W1[G,G+C], W2[G,2G+C] row-major, b0, b1, b2[G].  For point i, neighbour j:
+ *   e  = cat(x_i, x_j - x_i)                      y0 = relu(W0 e + b0)
+ *   s1 = relu(W1 cat(y0, x_i) + b1)               s2 = W2 cat(y0, x_i, s1) + b2          (no activation)
+ *   out[b,i,:] = max over the k neighbours of cat(y0, x_i, s1, s2)       channel order G, C, G, G as the reference has it
+ * The maximum starts from -inf (s2 may be negative for every neighbour) and skips NaN (fmaxf), where torch.max propagates it: a
+ * column that is NaN for every neighbour pools to -inf.  relu_out != 0 applies max(., 0) to the result (the caller's F.relu).
+ * out rows have stride ldo >= C + 3G; columns C + 3G .. ldo-1 are not touched, so the caller can point `out` into a wider
+ * buffer.  Products are fma chains in the reference's column order; the x_i columns of the three layers are evaluated once per
+ * point (W0's lead its chain, W1's and W2's are added to the per-edge part).  Served: C = 24 and C = 48, 1 <= k <= 32, N >= 1,
+ * B <= 65535; anything else is refused by name.  No [B, ., N, k] tensor exists anywhere. */
+int houv_dense_conv(const float* x, int ldx, const int32_t* idx, int B, int N, int C, int k, const float* W0, const float* b0,
+                    const float* W1, const float* b1, const float* W2, const float* b2, int relu_out, float* out, int ldo,
+                    void* stream);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
