@@ -72,6 +72,7 @@ _SIGNATURES = {
     "houv_pcn_fold": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_knn_feat": (ctypes.c_int, [_c_f, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_dense_conv": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 6 + [_int, _c_f, _int, _c_f]),
+    "houv_sa_attn": (ctypes.c_int, [_c_f, _int, _c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 5 + [_int, _c_f, _int, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

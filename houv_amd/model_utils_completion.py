@@ -235,7 +235,8 @@ class Conv1x1(nn.Module):
 
 class EF_expansion(nn.Module):
     """model_utils.py:24-55: x (B,input_size,N) -> (B,output_size,N*step_ratio), composed from houv_knn_feat, row gathers and
-    houv_gemm_f32 (not fused: ECG uses it only when num_points > num_coarse + num_input).  The reference's view / permute chain
+    houv_gemm_f32 (not fused: ECG uses it only when num_points > num_coarse + num_input; VRCNet's two expansions, 256 -> 64 and
+    64 -> 256, are the same code).  The reference's view / permute chain
     is kept: the (B,k,N,output_size*step_ratio) activations of conv2 are REINTERPRETED as (B,k,N*step_ratio,output_size)."""
 
     def __init__(self, input_size, output_size=64, step_ratio=2, k=4):
@@ -246,13 +247,13 @@ class EF_expansion(nn.Module):
         self.conv3 = Conv1x1(output_size, output_size, 2)
 
     @torch.no_grad()
-    def forward_rows(self, rows, idx=None, trace=None):
-        """rows (B,N,input_size) -> (B,N*step_ratio,output_size)."""
+    def forward_rows(self, rows, idx=None, trace=None, name="knn_exp"):
+        """rows (B,N,input_size) -> (B,N*step_ratio,output_size); `name`: the key under which a trace records the lists."""
         B, N, C = rows.shape
         if idx is None:
             idx = ops.knn_feat(rows, self.k)
         if trace is not None:
-            trace["knn_exp"], trace["knn_exp_x"] = idx, rows.clone()
+            trace[name], trace[name + "_x"] = idx, rows.clone()
         k = idx.shape[2]
         nb = _take_rows(rows, idx).permute(0, 2, 1, 3)                            # (B,k,N,C): the reference's B C K N as rows
         edge = torch.cat((rows.unsqueeze(1).expand_as(nb), nb), dim=3).contiguous()

@@ -1,0 +1,421 @@
+"""Mirror of completion/models/vrcnet.py (`SA_module` :21-67, `Folding` :70-113, `Linear_ResBlock` :116-127, `SK_SA_module`
+:130-188, `SKN_Res_unit` :191-224, `SA_SKN_Res_encoder` :227-362, `MSAP_SKN_decoder` :365-507, `Model` :510-656): the VRCNet
+completion network as an INFERENCE pipeline over the gfx950 kernels of include/houv_hip.h -- houv_mlp2_max for the PCN encoder
+it shares with models/pcn.py, one houv_gemm_f32 + houv_sa_attn per point self-attention block (the [B, C, k, N] edge tensor, its
+two projections and the [B, mid, k, N] weight tensor are never built), houv_gemm_f32 with the bias / ReLU / residual epilogue for
+every 1x1 convolution and linear layer, and the point ops (FPS, houv_knn, houv_knn_cross, three_nn) for the hierarchy.  Nothing
+goes through the host.  DESIGN.md section 9.11.
+
+Activations are rows [B, N, C].  The reference's torch.cat of [B, C, N] tensors are column slices of one row-major buffer per
+level: a SKN_Res_unit writes its level's features straight into the slice conv7..9 later read beside the up-sampled coarser
+level.  conv6 sees cat(global, x4) with the global feature constant over the points, so conv6.weight[:, :1024] g + bias is one
+vector per cloud (the split of EF_encoder.conv5); Folding's [B, 1024 + 64 + 2, num_fine] input is the sum of three such parts.
+
+The module tree and parameter names equal the reference's, so its checkpoints load with ``load_state_dict(strict=True)`` (the
+repository ships no trained weights: tests use seeded ones).  Training is NOT built: the "train" prefix doubles the batch, draws
+two latent samples and needs the KL / MMD terms (the reference's MMD branch also calls a method that does not exist); it raises
+NotImplementedError.
+
+Two things the reference does that are easy to miss and are kept: Linear_ResBlock's ReLU is in place, so its residual branch
+sees relu(feature) and the CALLER's tensor is rectified too -- the decoder receives relu(feat) + generator(z), not feat +
+generator(z); and SA_SKN_Res_encoder's decoder call hard-codes pts_num = [3072, 1536, 768, 384] and the `+ 2048` of up_scale.
+
+Discrete decisions.  ``Model(..., trace={})`` records every one of them, as models/ecg.py does: knn{level}_{i} for each level 1..4
+and each list i, fps1..3, knn_pt1..3, three_nn1..3, knn_exp1 (+ knn_exp1_x, the rows it was computed from) when up_scale >= 2,
+fps_out, topk, knn_exp2 (+ knn_exp2_x) when local_folding is off, plus feat (the PCN encoder's output) and z.  With trace=None
+nothing is recorded or copied."""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+from ..mm3d_pn2 import furthest_point_sample, knn_cross
+from ..model_utils_completion import Conv1x1, EF_expansion, _take_rows, calc_cd, calc_emd, gen_grid_up
+from .ecg import EF_encoder
+from .pcn import PCN_encoder
+
+
+def _linear(layer, x, relu=False, residual=None):
+    return ops.gemm(x, layer.weight, shift=layer.bias, residual=residual, relu=relu)
+
+
+def _flat(t):
+    """[B,N,C] rows (one row stride) -> [B*N,C] without a copy where the strides allow it."""
+    return t.reshape(-1, t.shape[-1]) if t.is_contiguous() else t.view(-1, t.shape[-1])
+
+
+class _Conv1x1NoBias(nn.Module):
+    """nn.Conv2d(n_in, n_out, 1, bias=False) as a parameter holder: weight [out, in, 1, 1], the reference's initialisation."""
+
+    def __init__(self, n_in, n_out):
+        super().__init__()
+        bound = 1 / np.sqrt(n_in)
+        self.weight = nn.Parameter(torch.empty((n_out, n_in, 1, 1)).uniform_(-bound, bound))
+
+    def matrix(self):
+        return self.weight.view(self.weight.shape[0], self.weight.shape[1])
+
+
+def _knn_rows(pts, k):
+    """pts (B,N,3) contiguous -> (B,N,k) int32, itself first: model_utils_completion.knn on rows."""
+    if k in (1, 3, 8, 16, 20) and k <= pts.shape[1]:
+        return ops.knn(pts, k)
+    return knn_cross(k, pts, pts)[1]
+
+
+class SA_module(nn.Module):
+    """vrcnet.py:21-67, the point self-attention block, for what SKN_Res_unit builds: in_planes = out_planes = C in {64, 128, 256,
+    512}, rel_planes = C/16, mid_planes = C/4, share_planes = 8 (houv_sa_attn serves these)."""
+
+    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=16):
+        super().__init__()
+        C = in_planes
+        if (C not in (64, 128, 256, 512) or out_planes != C or rel_planes != C // 16 or mid_planes != C // 4 or share_planes != 8
+                or not 1 <= k <= 32):
+            raise NotImplementedError(f"SA_module({in_planes}, {rel_planes}, {mid_planes}, {out_planes}, {share_planes}, k={k}) has no "
+                                      "kernel: C in (64, 128, 256, 512) with C/16, C/4, C, share_planes 8 and k <= 32 are served")
+        self.share_planes, self.k = share_planes, k
+        self.conv1 = Conv1x1(in_planes, rel_planes, 2)
+        self.conv2 = Conv1x1(in_planes, rel_planes, 2)
+        self.conv3 = Conv1x1(in_planes, mid_planes, 2)
+        self.conv_w = nn.Sequential(nn.ReLU(inplace=False), _Conv1x1NoBias(rel_planes * (k + 1), mid_planes // share_planes),
+                                    nn.ReLU(inplace=False), Conv1x1(mid_planes // share_planes, k * mid_planes // share_planes, 2))
+        self.conv_out = Conv1x1(mid_planes, out_planes, 2)
+
+    @torch.no_grad()
+    def forward_rows(self, x, idx, relu_out=False, out=None):
+        """x (B,N,C) rows (a column slice is fine), idx (B,N,k) int32 -> (B,N,C); relu_out: SK_SA_module's activation."""
+        B, N, C = x.shape
+        if idx.shape[2] != self.k:
+            raise ValueError(f"SA_module: built for k = {self.k}, got lists of {idx.shape[2]}")
+        W = torch.cat((self.conv1.matrix(), self.conv2.matrix(), self.conv3.matrix()), 0)
+        b = torch.cat((self.conv1.bias, self.conv2.bias, self.conv3.bias), 0)
+        P = ops.gemm(torch.relu(x).reshape(-1, C), W, shift=b).view(B, N, -1)
+        return ops.sa_attn(P, x, idx, self.conv_w[1].matrix(), self.conv_w[3].matrix(), self.conv_w[3].bias, self.conv_out.matrix(),
+                           self.conv_out.bias, relu_out=relu_out, out=out)
+
+    @torch.no_grad()
+    def forward(self, input):
+        """[x (B,C,1,N), idx (B,N,k)] -> [out (B,C,1,N), idx], the reference's layout."""
+        x, idx = input
+        rows = x.squeeze(2).transpose(1, 2).contiguous().float()
+        out = self.forward_rows(rows, idx.int().contiguous())
+        return [out.transpose(1, 2).unsqueeze(2).contiguous(), idx]
+
+
+class SK_SA_module(nn.Module):
+    """vrcnet.py:130-188: one SA_module per k-NN list, fused by a softmax over the branches.  With one list the softmax is exactly
+    1 and the result is relu(SA_module(x)) (fc / fcs exist, for the checkpoint, and are not evaluated)."""
+
+    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=(10, 20), r=2, L=32):
+        super().__init__()
+        self.num_kernels = len(k)
+        d = max(int(out_planes / r), L)
+        self.sams = nn.ModuleList([SA_module(in_planes, rel_planes, mid_planes, out_planes, share_planes, ki) for ki in k])
+        self.fc = nn.Linear(out_planes, d)
+        self.fcs = nn.ModuleList([nn.Linear(d, out_planes) for _ in k])
+
+    @torch.no_grad()
+    def forward_rows(self, x, idxs, out=None):
+        assert self.num_kernels == len(idxs)
+        if self.num_kernels == 1:
+            return self.sams[0].forward_rows(x, idxs[0], relu_out=True, out=out)
+        feas = [sam.forward_rows(x, idx, relu_out=True) for sam, idx in zip(self.sams, idxs)]
+        fea_s = sum(feas[1:], feas[0]).mean(dim=1)                                        # (B,C)
+        fea_z = _linear(self.fc, fea_s)
+        att = torch.softmax(torch.stack([_linear(fc, fea_z) for fc in self.fcs], dim=1), dim=1)        # (B,branches,C)
+        v = feas[0] * att[:, 0].unsqueeze(1)
+        for i in range(1, self.num_kernels):
+            v = v + feas[i] * att[:, i].unsqueeze(1)
+        if out is not None:
+            out.copy_(v)
+            return out
+        return v
+
+    @torch.no_grad()
+    def forward(self, input):
+        x, idxs = input
+        rows = x.squeeze(2).transpose(1, 2).contiguous().float()
+        out = self.forward_rows(rows, [i.int().contiguous() for i in idxs])
+        return [out.transpose(1, 2).unsqueeze(2).contiguous(), idxs]
+
+
+class SKN_Res_unit(nn.Module):
+    """vrcnet.py:191-224: conv2(relu(sam(conv1(feat)))) + conv_res(feat)."""
+
+    def __init__(self, input_size, output_size, k=(10, 20), layers=1):
+        super().__init__()
+        self.conv1 = _Conv1x1NoBias(input_size, output_size)
+        self.sam = nn.Sequential(*[SK_SA_module(output_size, output_size // 16, output_size // 4, output_size, 8, k)
+                                   for _ in range(int(layers))])
+        self.conv2 = _Conv1x1NoBias(output_size, output_size)
+        self.conv_res = _Conv1x1NoBias(input_size, output_size)
+
+    @torch.no_grad()
+    def forward_rows(self, feat, idxs, out=None, relu_out=False):
+        """feat (B,N,input_size) -> (B,N,output_size), written to `out` (a column slice is fine) when given."""
+        B, N, _ = feat.shape
+        f2 = _flat(feat)
+        x = ops.gemm(f2, self.conv1.matrix()).view(B, N, -1)
+        for layer in self.sam:
+            x = layer.forward_rows(x, idxs)
+        res = ops.gemm(f2, self.conv_res.matrix())
+        # self.af(x) is the identity here: an SK_SA_module's output is a convex combination of rectified branches
+        y = ops.gemm(x.view(B * N, -1), self.conv2.matrix(), None if out is None else _flat(out), residual=res,
+                     relu=relu_out)
+        return y.view(B, N, -1) if out is None else out
+
+
+class SA_SKN_Res_encoder(nn.Module):
+    """vrcnet.py:227-362 on rows: points (B,N,input_size), coordinates in columns 0..2 -> (B,N,output_size).  N must equal
+    pts_num[0] only in so far as the levels below it are sampled to pts_num[1..3] points."""
+
+    def __init__(self, input_size=3, k=(10, 20), pk=16, output_size=64, layers=(2, 2, 2, 2), pts_num=(3072, 1536, 768, 384)):
+        super().__init__()
+        self.init_channel = 64
+        c1 = self.init_channel
+        c2, c3, c4 = c1 * 2, c1 * 4, c1 * 8
+        self.sam_res1 = SKN_Res_unit(input_size, c1, k, int(layers[0]))
+        self.sam_res2 = SKN_Res_unit(c2, c2, k, int(layers[1]))
+        self.sam_res3 = SKN_Res_unit(c3, c3, k, int(layers[2]))
+        self.sam_res4 = SKN_Res_unit(c4, c4, k, int(layers[3]))
+        self.conv5 = Conv1x1(c4, 1024, 2)
+        self.fc1 = nn.Linear(1024, 512)
+        self.fc2 = nn.Linear(512, 1024)
+        self.conv6 = Conv1x1(c4 + 1024, c4, 2)
+        self.conv7 = Conv1x1(c3 + c4, c3, 2)
+        self.conv8 = Conv1x1(c2 + c3, c2, 2)
+        self.conv9 = Conv1x1(c1 + c2, c1, 2)
+        self.conv_out = Conv1x1(c1, output_size, 2)
+        self.k, self.pk, self.rate, self.pts_num = list(k), pk, 2, list(pts_num)
+        self.widths = (c1, c2, c3, c4)
+
+    def _lists(self, level, pts, trace):
+        out = []
+        for i, k in enumerate(self.k):
+            out.append(_knn_rows(pts, k))
+            if trace is not None:
+                trace[f"knn{level}_{i}"] = out[-1]
+        return out
+
+    def _pool(self, level, feat, pts, trace):
+        """edge_preserve_sampling (model_utils.py:90-116) on rows: feat (B,N,C), pts (B,N,3) -> (cat(centre, neighbour max)
+        (B,S,2C), the sampled points (B,S,3))."""
+        S, C = self.pts_num[level], feat.shape[2]
+        p_idx = furthest_point_sample(pts, S)
+        centres = _take_rows(pts, p_idx).contiguous()
+        pn_idx = knn_cross(int(min(self.pk, pts.shape[1])), centres, pts)[1]
+        if trace is not None:
+            trace[f"fps{level}"], trace[f"knn_pt{level}"] = p_idx, pn_idx
+        out = torch.empty((feat.shape[0], S, 2 * C), dtype=torch.float32, device=feat.device)
+        out[..., :C] = _take_rows(feat, p_idx)
+        out[..., C:] = _take_rows(feat, pn_idx).amax(dim=2)
+        return out, centres
+
+    @torch.no_grad()
+    def forward_rows(self, points, trace=None):
+        B, N, _ = points.shape
+        c1, c2, c3, c4 = self.widths
+        new = lambda n, c: torch.empty((B, n, c), dtype=torch.float32, device=points.device)
+        # one buffer per level: [the coarser level's features, up-sampled | the level's own], the operand of conv7..9
+        X1, X2, X3 = new(N, c2 + c1), new(self.pts_num[1], c3 + c2), new(self.pts_num[2], c4 + c3)
+        pt1 = points[..., :3].contiguous()
+        x1 = self.sam_res1.forward_rows(points, self._lists(1, pt1, trace), out=X1[..., c2:], relu_out=True)
+        f, pt2 = self._pool(1, x1, pt1, trace)
+        x2 = self.sam_res2.forward_rows(f, self._lists(2, pt2, trace), out=X2[..., c3:], relu_out=True)
+        f, pt3 = self._pool(2, x2, pt2, trace)
+        x3 = self.sam_res3.forward_rows(f, self._lists(3, pt3, trace), out=X3[..., c4:], relu_out=True)
+        f, pt4 = self._pool(3, x3, pt3, trace)
+        x4 = self.sam_res4.forward_rows(f, self._lists(4, pt4, trace), relu_out=True)
+
+        g = self.conv5.rows(x4).amax(dim=1)
+        g = _linear(self.fc2, _linear(self.fc1, g, relu=True), relu=True)                 # dropout: the identity at inference
+        W6 = self.conv6.matrix()
+        shift = ops.gemm(g, W6[:, :1024], shift=self.conv6.bias)                  # the global feature's share of conv6, per cloud
+        y = torch.relu_(ops.gemm(x4.view(-1, c4), W6[:, 1024:]).view(B, -1, c4) + shift.unsqueeze(1))
+        EF_encoder._upsample(1, y, pt3, pt4, X3[..., :c4], trace)
+        y = self.conv7.rows(X3, relu=True)
+        EF_encoder._upsample(2, y, pt2, pt3, X2[..., :c3], trace)
+        y = self.conv8.rows(X2, relu=True)
+        EF_encoder._upsample(3, y, pt1, pt2, X1[..., :c2], trace)
+        y = self.conv9.rows(X1, relu=True)
+        return self.conv_out.rows(y)
+
+    @torch.no_grad()
+    def forward(self, features):
+        """features (B,input_size,N) -> (B,output_size,N), the reference's layout."""
+        return self.forward_rows(features.transpose(1, 2).contiguous().float()).transpose(1, 2).contiguous()
+
+
+class Folding(nn.Module):
+    """vrcnet.py:70-113 on rows: (point_feat (B,n,input_size), global_feat (B,G)) -> (B,n*step_ratio,output_size).  The
+    [B, G + input_size + 2, n*step_ratio] input is never built: the pre-activation is the sum of conv.weight's global columns
+    (one vector per cloud), its point columns (one per coarse point) and its grid columns (one per grid cell)."""
+
+    def __init__(self, input_size, output_size, step_ratio, global_feature_size=1024, num_models=1):
+        super().__init__()
+        self.input_size, self.output_size, self.step_ratio, self.num_models = input_size, output_size, step_ratio, num_models
+        self.global_feature_size = global_feature_size
+        self.conv = Conv1x1(input_size + global_feature_size + 2, output_size, 1)
+        # (step_ratio, 2): the reference's factorisation loop and linspace (a 1-step axis is the single value -0.2); not a
+        # parameter and not in the state_dict, as in the reference, but it follows the module to its device
+        self.register_buffer("grid", gen_grid_up(step_ratio, 0.2).transpose(0, 1).contiguous(), persistent=False)
+
+    @torch.no_grad()
+    def forward_rows(self, point_feat, global_feat):
+        B, n, _ = point_feat.shape
+        W, G = self.conv.matrix(), self.global_feature_size
+        g = ops.gemm(global_feat, W[:, :G], shift=self.conv.bias)                                        # (B,out)
+        p = ops.gemm(_flat(point_feat), W[:, G:G + self.input_size]).view(B, n, 1, -1)
+        q = self.grid @ W[:, G + self.input_size:].t()                                                   # (step,out): 2 columns
+        return torch.relu_((p + g.view(B, 1, 1, -1)) + q.view(1, 1, self.step_ratio, -1)).view(B, n * self.step_ratio, -1)
+
+
+class Linear_ResBlock(nn.Module):
+    """vrcnet.py:116-127.  The reference's ReLU is in place: the residual branch sees relu(feature) too."""
+
+    def __init__(self, input_size=1024, output_size=256):
+        super().__init__()
+        self.conv1 = nn.Linear(input_size, input_size)
+        self.conv2 = nn.Linear(input_size, output_size)
+        self.conv_res = nn.Linear(input_size, output_size)
+
+    @torch.no_grad()
+    def forward(self, feature):
+        r = torch.relu(feature)
+        return _linear(self.conv2, _linear(self.conv1, r, relu=True), residual=_linear(self.conv_res, r))
+
+
+class MSAP_SKN_decoder(nn.Module):
+    """vrcnet.py:365-507: (global_feat (B,1024), input points (B,num_input,3)) -> (coarse_raw, coarse_high, coarse, fine), rows
+    of points."""
+
+    def __init__(self, num_coarse_raw, num_fps, num_coarse, num_fine, layers=(2, 2, 2, 2), knn_list=(10, 20), pk=10,
+                 points_label=False, local_folding=False):
+        super().__init__()
+        self.num_coarse_raw, self.num_fps, self.num_coarse, self.num_fine = num_coarse_raw, num_fps, num_coarse, num_fine
+        self.points_label, self.local_folding = points_label, local_folding
+        self.fc1 = nn.Linear(1024, 1024)
+        self.fc2 = nn.Linear(1024, 1024)
+        self.fc3 = nn.Linear(1024, num_coarse_raw * 3)
+        self.dense_feature_size, self.expand_feature_size = 256, 64
+        self.input_size = 4 if points_label else 3
+        self.encoder = SA_SKN_Res_encoder(input_size=self.input_size, k=knn_list, pk=pk, output_size=self.dense_feature_size,
+                                          layers=layers)
+        self.up_scale = int(np.ceil(num_fine / (num_coarse_raw + 2048)))
+        if self.up_scale >= 2:
+            self.expansion1 = EF_expansion(input_size=self.dense_feature_size, output_size=self.expand_feature_size,
+                                           step_ratio=self.up_scale, k=4)
+            self.conv_cup1 = Conv1x1(self.expand_feature_size, self.expand_feature_size)
+        else:
+            self.expansion1 = None
+            self.conv_cup1 = Conv1x1(self.dense_feature_size, self.expand_feature_size)
+        self.conv_cup2 = Conv1x1(self.expand_feature_size, 3)
+        self.conv_s1 = Conv1x1(self.expand_feature_size, 16)
+        self.conv_s2 = Conv1x1(16, 8)
+        self.conv_s3 = Conv1x1(8, 1)
+        if local_folding:
+            self.expansion2 = Folding(input_size=self.expand_feature_size, output_size=self.dense_feature_size,
+                                      step_ratio=num_fine // num_coarse)
+        else:
+            self.expansion2 = EF_expansion(input_size=self.expand_feature_size, output_size=self.dense_feature_size,
+                                           step_ratio=num_fine // num_coarse, k=4)
+        self.conv_f1 = Conv1x1(self.dense_feature_size, self.expand_feature_size)
+        self.conv_f2 = Conv1x1(self.expand_feature_size, 3)
+
+    @torch.no_grad()
+    def forward(self, global_feat, point_input, trace=None):
+        B = global_feat.shape[0]
+        raw = _linear(self.fc3, _linear(self.fc2, _linear(self.fc1, global_feat, relu=True), relu=True))
+        coarse_raw = raw.view(B, 3, self.num_coarse_raw).transpose(1, 2).contiguous()
+        points = torch.cat((coarse_raw, point_input), dim=1)
+        if self.points_label:
+            label = points.new_ones((B, points.shape[1], 1))
+            label[:, :self.num_coarse_raw] = 0
+            points = torch.cat((points, label), dim=2)
+        dense = self.encoder.forward_rows(points, trace)
+        if self.up_scale >= 2:
+            dense = self.expansion1.forward_rows(dense, trace=trace, name="knn_exp1")
+        feats = self.conv_cup1.rows(dense, relu=True)
+        coarse_high = self.conv_cup2.rows(feats)
+        coarse = coarse_high
+        if coarse.shape[1] > self.num_fps:
+            idx = furthest_point_sample(coarse_high, self.num_fps)
+            if trace is not None:
+                trace["fps_out"] = idx
+            coarse, feats = _take_rows(coarse_high, idx).contiguous(), _take_rows(feats, idx).contiguous()
+        if coarse.shape[1] > self.num_coarse:
+            s = self.conv_s3.rows(self.conv_s2.rows(self.conv_s1.rows(feats, relu=True), relu=True))
+            idx = F.softplus(s).view(B, -1).topk(self.num_coarse, dim=1)[1].int()
+            if trace is not None:
+                trace["topk"] = idx
+            coarse, feats = _take_rows(coarse, idx).contiguous(), _take_rows(feats, idx).contiguous()
+        if coarse.shape[1] < self.num_fine:
+            step = self.num_fine // self.num_coarse
+            if self.local_folding:
+                up = self.expansion2.forward_rows(feats, global_feat)
+                centre = coarse.unsqueeze(2).expand(-1, -1, step, -1).reshape(B, self.num_fine, 3)
+                fine = self.conv_f2.rows(self.conv_f1.rows(up, relu=True)) + centre
+            else:
+                up = self.expansion2.forward_rows(feats, trace=trace, name="knn_exp2")
+                fine = self.conv_f2.rows(self.conv_f1.rows(up, relu=True))
+        else:
+            assert coarse.shape[1] == self.num_fine
+            fine = coarse
+        return coarse_raw, coarse_high, coarse, fine
+
+
+class Model(nn.Module):
+    """``Model(args, size_z=128, global_feature_size=1024, trace=None).forward(x[B,3,N], gt=None, prefix="train",
+    mean_feature=None, alpha=None, z=None)`` (vrcnet.py:510-656).  ``args``: layers, knn_list (comma-separated strings),
+    distribution_loss, loss, eval_emd, num_fps, num_points, num_coarse, num_coarse_raw, pk, local_folding, points_label
+    (cfgs/vrcnet_mi355x.yaml).
+
+    "test": {'result': fine}.  "val": the reference's dictionary out1 (coarse_raw), out2 (fine), cd_p, cd_t, f1, and 'emd' as well
+    when eval_emd is set (the reference computes it and drops it).  "train" raises NotImplementedError: it is out of scope.
+
+    The reference draws the latent z = q.rsample() even under "test"; ``z`` (B,size_z), when given, replaces the sample, and
+    with z=None q_mu + softplus(q_std) * randn is drawn on the device (torch's generator: seed it for a repeatable result)."""
+
+    def __init__(self, args, size_z=128, global_feature_size=1024, trace=None):
+        super().__init__()
+        layers = [int(i) for i in str(args.layers).split(',')]
+        knn_list = [int(i) for i in str(args.knn_list).split(',')]
+        self.size_z = size_z
+        self.distribution_loss, self.train_loss, self.eval_emd = args.distribution_loss, args.loss, args.eval_emd
+        self.trace = trace
+        self.encoder = PCN_encoder(output_size=global_feature_size)
+        self.posterior_infer1 = Linear_ResBlock(input_size=global_feature_size, output_size=global_feature_size)
+        self.posterior_infer2 = Linear_ResBlock(input_size=global_feature_size, output_size=size_z * 2)
+        self.prior_infer = Linear_ResBlock(input_size=global_feature_size, output_size=size_z * 2)
+        self.generator = Linear_ResBlock(input_size=size_z, output_size=global_feature_size)
+        self.decoder = MSAP_SKN_decoder(num_fps=args.num_fps, num_fine=args.num_points, num_coarse=args.num_coarse,
+                                        num_coarse_raw=args.num_coarse_raw, layers=layers, knn_list=knn_list, pk=args.pk,
+                                        local_folding=args.local_folding, points_label=args.points_label)
+
+    @torch.no_grad()
+    def forward(self, x, gt=None, prefix="train", mean_feature=None, alpha=None, z=None):
+        if prefix == "train":
+            raise NotImplementedError('VRCNet: the "train" prefix (doubled batch, two latent samples, KL / MMD terms) is not built')
+        rows = x.transpose(1, 2).contiguous().float()
+        feat = self.encoder(rows)
+        o_x = self.posterior_infer2(self.posterior_infer1(feat))
+        q_mu, q_std = torch.split(o_x, self.size_z, dim=1)
+        if z is None:
+            z = q_mu + F.softplus(q_std) * torch.randn_like(q_mu)
+        z = z.to(feat.dtype).contiguous()
+        if self.trace is not None:
+            self.trace["feat"], self.trace["z"] = feat, z
+        # posterior_infer1's in-place ReLU has rectified feat by the time the reference adds the generator's output to it
+        global_feat = torch.relu(feat) + self.generator(z)
+        coarse_raw, coarse_high, coarse, fine = self.decoder(global_feat, rows, self.trace)
+        if self.trace is not None:
+            self.trace.update(coarse_raw=coarse_raw, coarse_high=coarse_high, coarse=coarse, fine=fine)
+        if prefix == "val":
+            cd_p, cd_t, f1 = calc_cd(fine, gt, calc_f1=True)
+            res = {'out1': coarse_raw, 'out2': fine, 'cd_p': cd_p, 'cd_t': cd_t, 'f1': f1}
+            if self.eval_emd:
+                res['emd'] = calc_emd(fine, gt, eps=0.004, iterations=3000)
+            return res
+        return {'result': fine}

@@ -508,6 +508,47 @@ def dense_conv(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# VRCNet completion network (houv_sa_attn)
+# ---------------------------------------------------------------------------------------------------
+SA_ATTN_BLOCK = 128                        # HOUV_SA_ATTN_BLOCK: points per workgroup
+
+
+def sa_attn(P, x, idx, Ww1, Ww2, bw2, Wout, bout, relu_out=False, out=None):
+    """SA_module.forward (completion/models/vrcnet.py:49-67) after its input projections, in one kernel (houv_sa_attn).  With
+    rel = C/16, mid = C/4, m = mid/8: P[B,N,2 rel + mid] = relu(x) . [W1; W2; W3]^T + bias (columns x1 | x2 | x3, one `gemm`),
+    x[B,N,C] the pre-activation identity, idx[B,N,k] int32, Ww1[m, rel (k+1)], Ww2[k m, m], bw2[k m], Wout[C, mid], bout[C] ->
+    out[B,N,C] = Wout relu(sum_j w_j x3_j) + bout + x, relu applied when relu_out.  C = 64, 128, 256 or 512, k <= 32.  P, x and
+    `out` may be column slices of wider row-major buffers (P's row stride a multiple of 4, its address of 16 bytes); `out` may be
+    x itself."""
+    _lib.require_gpu_any(P, x, Ww1, Ww2, bw2, Wout, bout, out)
+    _lib.require_gpu(idx, Ww1, Ww2, bw2, Wout, bout); _want(idx, _I32, "sa_attn: idx")
+    B, N, C, ldx = _rows(x, "sa_attn: x")
+    rel, mid, m = C // 16, C // 4, C // 32
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.HouvHipError(f"sa_attn: expected idx[{B},{N},k], got {tuple(idx.shape)}")
+    k = idx.shape[2]
+    if tuple(P.shape) != (B, N, 2 * rel + mid):
+        raise _lib.HouvHipError(f"sa_attn: expected P[{B},{N},{2 * rel + mid}], got {tuple(P.shape)}")
+    ldp = _rows(P, "sa_attn: P")[3]
+    if tuple(Ww1.shape) != (m, rel * (k + 1)) or tuple(Ww2.shape) != (k * m, m) or bw2.numel() != k * m \
+            or tuple(Wout.shape) != (C, mid) or bout.numel() != C:
+        raise _lib.HouvHipError(f"sa_attn: expected Ww1[{m},{rel * (k + 1)}], Ww2[{k * m},{m}], bw2[{k * m}], Wout[{C},{mid}], "
+                                f"bout[{C}], got {tuple(Ww1.shape)}, {tuple(Ww2.shape)}, {tuple(bw2.shape)}, {tuple(Wout.shape)}, "
+                                f"{tuple(bout.shape)}")
+    if out is None:
+        out = torch.empty((B, N, C), dtype=_F32, device=x.device)
+    if tuple(out.shape) != (B, N, C):
+        raise _lib.HouvHipError(f"sa_attn: out must be [{B},{N},{C}], got {tuple(out.shape)}")
+    ldo = _rows(out, "sa_attn: out")[3]
+    with torch.cuda.device(x.device):
+        ok = _lib.load().houv_sa_attn(ctypes_ptr(P), ldp, ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, k, _lib.ptr(Ww1),
+                                      _lib.ptr(Ww2), _lib.ptr(bw2), _lib.ptr(Wout), _lib.ptr(bout), int(bool(relu_out)),
+                                      ctypes_ptr(out), ldo, _lib.stream_of(x))
+    _lib.check(ok, "houv_sa_attn")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------
 _registered = False
@@ -547,6 +588,8 @@ def register_torch_ops():
     lib.define("pcn_fold(Tensor coarse, Tensor cvec, Tensor grid, Tensor Wgp, Tensor W2, Tensor b2, Tensor W3, Tensor b3) -> Tensor")
     lib.define("knn_feat(Tensor x, int k) -> (Tensor, Tensor)")
     lib.define("dense_conv(Tensor x, Tensor idx, Tensor W0, Tensor b0, Tensor W1, Tensor b1, Tensor W2, Tensor b2, "
+               "bool relu_out) -> Tensor")
+    lib.define("sa_attn(Tensor P, Tensor x, Tensor idx, Tensor Ww1, Tensor Ww2, Tensor bw2, Tensor Wout, Tensor bout, "
                "bool relu_out) -> Tensor")
     lib.impl("chamfer_forward", chamfer_forward, "CUDA")
     lib.impl("chamfer_backward", chamfer_backward, "CUDA")
@@ -588,6 +631,7 @@ def register_torch_ops():
         return knn_feat(x, k, want_dist=True)
     lib.impl("knn_feat", _knn_feat, "CUDA")
     lib.impl("dense_conv", dense_conv, "CUDA")
+    lib.impl("sa_attn", sa_attn, "CUDA")
     register_torch_ops._lib = lib      # keep alive
     _registered = True
 

@@ -474,6 +474,35 @@ int houv_dense_conv(const float* x, int ldx, const int32_t* idx, int B, int N, i
                     const float* W1, const float* b1, const float* W2, const float* b2, int relu_out, float* out, int ldo,
                     void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * VRCNet completion network (completion/models/vrcnet.py).  The same promises as the ECG block above. */
+
+/* Points per workgroup of houv_sa_attn: the size at whose edges a partial workgroup begins. */
+#define HOUV_SA_ATTN_BLOCK 128
+
+/* SA_module.forward (vrcnet.py:49-67) after its three input projections.  With rel = C/16, mid = C/4, m = mid/8 (share_planes =
+ * 8), the caller first writes, with one GEMM per point, P[B,N,2 rel + mid] = relu(x) . [W1; W2; W3]^T + [b1; b2; b3], columns
+ * [x1 | x2 | x3], rows of stride ldp.  idx[B,N,k] are neighbour lists into the SAME cloud (an entry outside 0..N-1 is clamped into
+ * that range: nothing outside P is read).  For point n:
+ *   t[0 .. rel)        = x1[n]
+ *   t[rel + r k + j]   = x2[idx[n,j]][r]                     channel-major, neighbour-minor: the reference's x2.view(B,-1,1,N)
+ *   h    = relu(Ww1 relu(t))                                 Ww1[m, rel (k+1)] row-major, no bias
+ *   w    = Ww2 h + bw2                                       Ww2[k m, m], bw2[k m];  w[c', j] = w[c' k + j]
+ *   o[c] = sum over j of w[c mod m, j] x3[idx[n,j]][c]       c in [0, mid): repeat(1, share, 1, 1) tiles the m rows
+ *   out[n] = (Wout relu(o) + bout) + x[n]                    Wout[C, mid], bout[C]; x is the PRE-activation identity
+ * and relu_out != 0 applies max(., 0) to the result (SK_SA_module's activation).  Every product is an fp32 fma chain in the
+ * order written (t: x1 first, then neighbour by neighbour, r ascending; j, q ascending elsewhere).  fmaxf drops a NaN where
+ * torch.relu keeps it.
+ * x rows have stride ldx >= C, out rows ldo >= C: both may be column slices of wider buffers, and columns C .. ldo-1 of out are
+ * not touched.  ldp >= 2 rel + mid must be a multiple of 4 and P aligned to 16 bytes (its rows are read four floats at a time).
+ * `out` may be `x` itself (the same pointer and ldo == ldx): an element of x is read only by the lane that then writes it.  The
+ * same pointer with ldo != ldx is refused; any other overlap of out with x or P is the caller's error and is not detected.
+ * Served: C = 64, 128, 256, 512; 1 <= k <= 32; k <= N <= 16384; B <= 65535 (B = 0 launches nothing); anything else, and a NULL
+ * pointer, is refused by name.  No [B, ., k, N] tensor exists anywhere. */
+int houv_sa_attn(const float* P, int ldp, const float* x, int ldx, const int32_t* idx, int B, int N, int C, int k,
+                 const float* Ww1, const float* Ww2, const float* bw2, const float* Wout, const float* bout, int relu_out,
+                 float* out, int ldo, void* stream);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
