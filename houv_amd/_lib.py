@@ -69,7 +69,15 @@ _SIGNATURES = {
     "houv_edge_diff": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _int, _c_f, _c_f]),
     "houv_mlp2_max": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, ctypes.c_longlong, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
     "houv_mlp2_max_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
+    "houv_mlp2_max_arg": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, ctypes.c_longlong, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "houv_mlp2_max_arg_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
+    "houv_mlp2_max_backward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, ctypes.c_longlong, _c_f, _int, _c_f, _c_f,
+                                              _c_f, _c_f, _c_f, _int] + [_c_f] * 9),
+    "houv_mlp2_max_backward_workspace_bytes": (ctypes.c_longlong, [_int] * 6),
+    "houv_mlp2_max_backward_rows": (ctypes.c_int, [_int, _int, _int]),
     "houv_pcn_fold": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "houv_pcn_fold_backward": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _int] + [_c_f] * 14 + [ctypes.c_longlong, _c_f]),
+    "houv_pcn_fold_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
     "houv_knn_feat": (ctypes.c_int, [_c_f, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_dense_conv": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 6 + [_int, _c_f, _int, _c_f]),
     "houv_sa_attn": (ctypes.c_int, [_c_f, _int, _c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 5 + [_int, _c_f, _int, _c_f]),

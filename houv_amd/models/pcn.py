@@ -10,8 +10,11 @@ points, so conv3.weight[:, 256:] g1 + bias is one 512-vector per cloud (the `shi
 sees cat(grid, point, global), so conv1.weight[:, 5:] feat + bias is one 512-vector per cloud (`cvec`).
 
 The module tree and parameter names equal the reference's, so its checkpoints load with ``load_state_dict(strict=True)`` (the
-repository ships no trained weights: tests use seeded ones).  Training is NOT built: the "train" prefix returns the reference's
-tuple computed forward-only, without a graph.  `PCN_Transformer` and `PCN_encoder_label` are not built."""
+repository ships no trained weights: tests use seeded ones).  Training is opt-in: ``Model(args, num_coarse,
+trainable=True)`` runs the encoder (houv_mlp2_max_arg + houv_mlp2_max_backward on the critical points of each cloud), the three
+linear layers and the folding stage (houv_pcn_fold_backward, which recomputes what the forward did not keep) through
+``torch.autograd.Function``s, and its "train" prefix returns the reference's tuple with a graph.  With the
+default ``trainable=False`` the tuple is computed forward-only, without a graph.  `PCN_Transformer` and `PCN_encoder_label` are not built."""
 import math
 
 import torch
@@ -43,22 +46,71 @@ class _Conv1x1(nn.Module):
         return cache[(lo, hi)][1]
 
 
+def _transposed(a):
+    """a[m,n] -> a fresh, densely packed [n,m].  Not ``a.t().contiguous()``: with m == 1 torch already calls the transposed view
+    contiguous and returns it as it is, with a last stride of n, which the GEMM (unit last stride) refuses -- a batch of one
+    cloud would not train."""
+    out = torch.empty((a.shape[1], a.shape[0]), dtype=a.dtype, device=a.device)
+    out.copy_(a.t())
+    return out
+
+
 def _linear(layer, x, relu=False):
     return ops.gemm(x, layer.weight, shift=layer.bias, relu=relu)
 
 
-class PCN_encoder(nn.Module):
-    """pcn.py:12-29 on rows: x[B,N,3] -> global feature [B,1024]."""
+class _EncoderFunction(torch.autograd.Function):
+    """The whole encoder as one differentiable node.  Forward: the two PointNet blocks through
+    houv_mlp2_max_arg, bit for bit the inference path's feature.  Backward: both maxima send their gradient to one row per
+    channel, so block 2 runs on its <= 1024 critical rows per cloud and hands block 1 the gradient of y on exactly those rows
+    (a row list, never a dense [B,N,256] tensor); block 1 adds its own <= 256.  The pooled half of cat(y, g1) was split off
+    into shift1 = W3[:, 256:] g1 + b3, so its three gradients are small products of gshift1[B,512]."""
 
-    def __init__(self, output_size=1024):
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, W3, b3, W4, b4, W3y):
+        g1, arg1, y = ops.mlp2_max_arg(x, W1, b1, W2, b2, want_y=True)
+        shift1 = ops.gemm(g1, W3[:, 256:], shift=b3)
+        feat, arg2, _ = ops.mlp2_max_arg(y, W3y, shift1, W4, b4)
+        ctx.save_for_backward(x, W1, b1, W2, W3, W4, W3y, y, g1, shift1, arg1, arg2)
+        return feat
+
+    @staticmethod
+    def backward(ctx, gfeat):
+        x, W1, b1, W2, W3, W4, W3y, y, g1, shift1, arg1, arg2 = ctx.saved_tensors
+        r2 = ops.mlp2_max_backward(y, W3y, shift1, W4, arg2, gfeat.contiguous(), want_gx=True)
+        gs = r2["gshift1"]                                                       # [B,512]: one row per cloud
+        gW3 = torch.empty_like(W3)
+        gW3[:, :256] = r2["gW1"]
+        ops.gemm(_transposed(gs), _transposed(g1), gW3[:, 256:])         # gshift1^T g1
+        gg1 = ops.gemm(gs, W3[:, 256:], trans_b=False)                           # what shift1 sends back to the first pool
+        r1 = ops.mlp2_max_backward(x, W1, b1, W2, arg1, gg1, rows=r2["act_rows"], nrows=r2["nact"], gy_rows=r2["gx_rows"])
+        return None, r1["gW1"], r1["gshift1"].sum(0), r1["gW2"], r1["gb2"], gW3, gs.sum(0), r2["gW2"], r2["gb2"], None
+
+
+class PCN_encoder(nn.Module):
+    """pcn.py:12-29 on rows: x[B,N,3] -> global feature [B,1024].  ``trainable=True`` makes the feature differentiable with
+    respect to the eight parameters when grad mode is on (the same bits; not with respect to x, which is refused)."""
+
+    def __init__(self, output_size=1024, trainable=False):
         super().__init__()
+        self.trainable = trainable
         self.conv1 = _Conv1x1(3, 128)
         self.conv2 = _Conv1x1(128, 256)
         self.conv3 = _Conv1x1(512, 512)
         self.conv4 = _Conv1x1(512, output_size)
 
-    @torch.no_grad()
     def forward(self, x):
+        if self.trainable and torch.is_grad_enabled():
+            if x.requires_grad:
+                raise ValueError("PCN_encoder: the gradient with respect to the input cloud is not built (x.requires_grad)")
+            with torch.no_grad():
+                W3y = self.conv3.columns(0, 256)                                 # a packed copy: its gradient returns through W3
+            return _EncoderFunction.apply(x, self.conv1.matrix(), self.conv1.bias, self.conv2.matrix(), self.conv2.bias,
+                                          self.conv3.matrix(), self.conv3.bias, self.conv4.matrix(), self.conv4.bias, W3y)
+        with torch.no_grad():
+            return self._forward(x)
+
+    def _forward(self, x):
         g1, y = ops.mlp2_max(x, self.conv1.matrix(), self.conv1.bias, self.conv2.matrix(), self.conv2.bias, want_y=True)
         W3 = self.conv3.matrix()
         shift1 = ops.gemm(g1, W3[:, 256:], shift=self.conv3.bias)               # the pooled half of cat(y, g1): once per cloud
@@ -66,11 +118,52 @@ class PCN_encoder(nn.Module):
         return feat
 
 
-class PCN_decoder(nn.Module):
-    """pcn.py:86-126: feat[B,1024] -> (coarse[B,num_coarse,3], fine[B,num_fine,3]), both as rows of points."""
+class _LinearFunction(torch.autograd.Function):
+    """relu?(x W^T + b) over ops.gemm, with its backward over ops.gemm: gx = gz W, gW = gz^T x, gb = sum gz, gz = gy * [y > 0]."""
 
-    def __init__(self, num_coarse, num_fine, scale, cat_feature_num):
+    @staticmethod
+    def forward(ctx, x, W, b, relu):
+        y = ops.gemm(x, W, shift=b, relu=relu)
+        ctx.relu = relu
+        ctx.save_for_backward(x, W, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, W, y = ctx.saved_tensors
+        gz = (gy * (y > 0)).contiguous() if ctx.relu else gy.contiguous()
+        return ops.gemm(gz, W, trans_b=False), ops.gemm(_transposed(gz), _transposed(x)), gz.sum(0), None
+
+
+class _FoldFunction(torch.autograd.Function):
+    """The folding stage with the `cvec` split as one differentiable node: houv_pcn_fold forward (nothing kept but its inputs),
+    houv_pcn_fold_backward backward.  conv1.weight = [Wgp | Wf]: gWgp comes from the kernel, gWf = gcvec^T feat,
+    g(conv1.bias) = sum_b gcvec, and gcvec Wf joins the gradient of the global feature."""
+
+    @staticmethod
+    def forward(ctx, coarse, feat, grid, W1, b1, Wgp, W2, b2, W3, b3):
+        cvec = ops.gemm(feat, W1[:, 5:], shift=b1)
+        ctx.save_for_backward(coarse, feat, grid, W1, Wgp, W2, b2, W3, b3, cvec)
+        return ops.pcn_fold(coarse, cvec, grid, Wgp, W2, b2, W3, b3)
+
+    @staticmethod
+    def backward(ctx, gfine):
+        coarse, feat, grid, W1, Wgp, W2, b2, W3, b3, cvec = ctx.saved_tensors
+        r = ops.pcn_fold_backward(coarse, cvec, grid, Wgp, W2, b2, W3, b3, gfine.contiguous())
+        gW1 = torch.empty_like(W1)
+        gW1[:, :5] = r["gWgp"]
+        ops.gemm(_transposed(r["gcvec"]), _transposed(feat), gW1[:, 5:])
+        gfeat = ops.gemm(r["gcvec"], W1[:, 5:], trans_b=False)
+        return r["gcoarse"], gfeat, None, gW1, r["gcvec"].sum(0), None, r["gW2"], r["gb2"], r["gW3"], r["gb3"]
+
+
+class PCN_decoder(nn.Module):
+    """pcn.py:86-126: feat[B,1024] -> (coarse[B,num_coarse,3], fine[B,num_fine,3]), both as rows of points.  ``trainable=True``:
+    differentiable with respect to feat and the twelve parameters when grad mode is on (the same bits)."""
+
+    def __init__(self, num_coarse, num_fine, scale, cat_feature_num, trainable=False):
         super().__init__()
+        self.trainable = trainable
         if scale < 1 or scale & (scale - 1) or num_coarse * scale != num_fine:
             raise ValueError(f"PCN_decoder: scale = num_fine // num_coarse = {scale} must be a power of two with "
                              f"num_coarse * scale == num_fine (got num_coarse={num_coarse}, num_fine={num_fine})")
@@ -83,15 +176,27 @@ class PCN_decoder(nn.Module):
         self.conv2 = _Conv1x1(512, 512)
         self.conv3 = _Conv1x1(512, 3)
 
-    @torch.no_grad()
     def forward(self, x):
+        if self.grid.device != x.device:
+            self.grid = self.grid.to(x.device)
+        if self.trainable and torch.is_grad_enabled():
+            lin = lambda layer, t, relu: _LinearFunction.apply(t, layer.weight, layer.bias, relu)
+            coarse = lin(self.fc3, lin(self.fc2, lin(self.fc1, x, True), True), False)
+            coarse = coarse.view(x.shape[0], 3, self.num_coarse).transpose(1, 2).contiguous()
+            with torch.no_grad():
+                Wgp = self.conv1.columns(0, 5)                                   # a packed copy: its gradient returns through W1
+            fine = _FoldFunction.apply(coarse, x, self.grid, self.conv1.matrix(), self.conv1.bias, Wgp, self.conv2.matrix(),
+                                       self.conv2.bias, self.conv3.matrix(), self.conv3.bias)
+            return coarse, fine
+        with torch.no_grad():
+            return self._forward(x)
+
+    def _forward(self, x):
         B = x.shape[0]
         coarse = _linear(self.fc3, _linear(self.fc2, _linear(self.fc1, x, relu=True), relu=True))
         coarse = coarse.view(B, 3, self.num_coarse).transpose(1, 2).contiguous()                 # [B,nc,3]
         W1 = self.conv1.matrix()
         cvec = ops.gemm(x, W1[:, 5:], shift=self.conv1.bias)                    # the global feature's share of conv1, per cloud
-        if self.grid.device != x.device:
-            self.grid = self.grid.to(x.device)
         fine = ops.pcn_fold(coarse, cvec, self.grid, self.conv1.columns(0, 5), self.conv2.matrix(), self.conv2.bias,
                             self.conv3.matrix(), self.conv3.bias)
         return coarse, fine
@@ -101,21 +206,34 @@ class Model(nn.Module):
     """``Model(args, num_coarse=1024).forward(x[B,3,N], gt=None, prefix="train", mean_feature=None, alpha=None)`` (pcn.py:129-182).
     ``args``: num_points, loss ('cd' | 'emd'), eval_emd (cfgs/pcn_mi355x.yaml).  "test": {'result': out2}; "val": out1, out2, cd_p,
     cd_t, f1 (the reference computes an `emd` there when eval_emd is set and throws it away: not computed); "train": (out2, loss2,
-    total_train_loss), forward only.  out1 [B,num_coarse,3], out2 [B,num_points,3]."""
+    total_train_loss).  out1 [B,num_coarse,3], out2 [B,num_points,3].
 
-    def __init__(self, args, num_coarse=1024):
+    ``trainable=False`` (the default): everything is computed without a graph, "train" included.  ``trainable=True`` with grad
+    mode on: the same outputs and losses bit for bit, with a graph through the encoder, decoder and loss, so that
+    ``total_train_loss.backward()`` fills ``.grad`` of all 20 parameters and ``torch.optim.Adam(net.parameters())`` trains as
+    completion/train.py does.  The gradient with respect to the input cloud is not built: an x with requires_grad is refused."""
+
+    def __init__(self, args, num_coarse=1024, trainable=False):
         super().__init__()
+        self.trainable = trainable
         self.num_coarse = num_coarse
         self.num_points = args.num_points
         self.train_loss = args.loss
         self.eval_emd = args.eval_emd
         self.scale = self.num_points // num_coarse
         self.cat_feature_num = 2 + 3 + 1024
-        self.encoder = PCN_encoder()
-        self.decoder = PCN_decoder(num_coarse, self.num_points, self.scale, self.cat_feature_num)
+        self.encoder = PCN_encoder(trainable=trainable)
+        self.decoder = PCN_decoder(num_coarse, self.num_points, self.scale, self.cat_feature_num, trainable=trainable)
 
-    @torch.no_grad()
     def forward(self, x, gt=None, prefix="train", mean_feature=None, alpha=None):
+        if self.trainable and torch.is_grad_enabled():
+            if x.requires_grad:
+                raise ValueError("models.pcn.Model: the gradient with respect to the input cloud is not built (x.requires_grad)")
+            return self._forward(x, gt, prefix, alpha)
+        with torch.no_grad():
+            return self._forward(x, gt, prefix, alpha)
+
+    def _forward(self, x, gt, prefix, alpha):
         feat = self.encoder(x.transpose(1, 2).contiguous().float())
         out1, out2 = self.decoder(feat)
         if prefix == "train":

@@ -425,6 +425,96 @@ def mlp2_max(x, W1, shift1, W2, b2, want_y=False):
     return pooled, y
 
 
+def mlp2_max_arg(x, W1, shift1, W2, b2, want_y=False):
+    """mlp2_max that also says where each maximum sits (houv_mlp2_max_arg): the same arguments ->
+    (pooled[B,Cout], arg[B,Cout] int32, y or None).  pooled and y carry mlp2_max's bits; arg[b,c] is the lowest n with
+    y[b,n,c] == pooled[b,c] (torch.max's rule on the CPU), -1 for a column that is NaN in every row."""
+    _lib.require_gpu(x, W1, shift1, W2, b2)
+    for t, n in ((x, "x"), (W1, "W1"), (shift1, "shift1"), (W2, "W2"), (b2, "b2")):
+        _want(t, _F32, f"mlp2_max_arg: {n}")
+    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0] \
+            or b2.numel() != W2.shape[0]:
+        raise _lib.HouvHipError(f"mlp2_max_arg: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H], b2[Cout], got {tuple(x.shape)}, "
+                                f"{tuple(W1.shape)}, {tuple(W2.shape)}, {tuple(b2.shape)}")
+    B, N, Cin = x.shape
+    H, Cout = W1.shape[0], W2.shape[0]
+    if tuple(shift1.shape) == (H,):
+        stride = 0
+    elif tuple(shift1.shape) == (B, H):
+        stride = H
+    else:
+        raise _lib.HouvHipError(f"mlp2_max_arg: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    dev = x.device
+    pooled = torch.empty((B, Cout), dtype=_F32, device=dev)
+    arg = torch.empty((B, Cout), dtype=_I32, device=dev)
+    y = torch.empty((B, N, Cout), dtype=_F32, device=dev) if want_y else None
+    lib = _lib.load()
+    nbytes = lib.houv_mlp2_max_arg_workspace_bytes(B, N, Cout)
+    ws = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes > 0 else None
+    with torch.cuda.device(dev):
+        ok = lib.houv_mlp2_max_arg(_lib.ptr(x), B, N, Cin, _lib.ptr(W1), H, _lib.ptr(shift1), stride, _lib.ptr(W2), _lib.ptr(b2),
+                                   Cout, _lib.ptr(pooled), _lib.ptr(arg), _lib.ptr(y), _lib.ptr(ws), _lib.stream_of(x))
+    _lib.check(ok, "houv_mlp2_max_arg")
+    return pooled, arg, y
+
+
+def mlp2_max_backward(x, W1, shift1, W2, arg, gpooled, rows=None, nrows=None, gy_rows=None, want_gx=False):
+    """The backward pass of one PointNet block on its active rows only (houv_mlp2_max_backward).
+    x, W1, shift1, W2 as in mlp2_max; arg[B,Cout] int32 from mlp2_max_arg; gpooled[B,Cout]; optionally a gradient on y carried
+    on rows[B,R] int32 (strictly ascending in the first nrows[b] entries), nrows[B] int32, gy_rows[B,R,Cout].
+    -> dict(gW1[H,Cin], gshift1[B,H], gW2[Cout,H], gb2[Cout], act_rows[B,Rcap] int32, nact[B] int32, gx_rows[B,Rcap,Cin] or
+    None): act_rows lists each cloud's active rows ascending (-1 past nact[b]) and gx_rows holds the input gradient of those
+    rows (zeros past nact[b]) -- the (rows, nrows, gy_rows) of the block below."""
+    ts = (x, W1, shift1, W2, gpooled)
+    _lib.require_gpu(*ts, arg)
+    for t, n in zip(ts, ("x", "W1", "shift1", "W2", "gpooled")):
+        _want(t, _F32, f"mlp2_max_backward: {n}")
+    _want(arg, _I32, "mlp2_max_backward: arg")
+    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0]:
+        raise _lib.HouvHipError(f"mlp2_max_backward: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H], got {tuple(x.shape)}, "
+                                f"{tuple(W1.shape)}, {tuple(W2.shape)}")
+    B, N, Cin = x.shape
+    H, Cout = W1.shape[0], W2.shape[0]
+    if tuple(arg.shape) != (B, Cout) or tuple(gpooled.shape) != (B, Cout):
+        raise _lib.HouvHipError(f"mlp2_max_backward: arg and gpooled must be [{B},{Cout}], got {tuple(arg.shape)}, {tuple(gpooled.shape)}")
+    if tuple(shift1.shape) == (H,):
+        stride = 0
+    elif tuple(shift1.shape) == (B, H):
+        stride = H
+    else:
+        raise _lib.HouvHipError(f"mlp2_max_backward: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    R = 0
+    if rows is not None or nrows is not None or gy_rows is not None:
+        if rows is None or nrows is None or gy_rows is None:
+            raise _lib.HouvHipError("mlp2_max_backward: rows, nrows and gy_rows come together")
+        _lib.require_gpu(rows, nrows, gy_rows)
+        _want(rows, _I32, "mlp2_max_backward: rows"); _want(nrows, _I32, "mlp2_max_backward: nrows")
+        _want(gy_rows, _F32, "mlp2_max_backward: gy_rows")
+        if rows.dim() != 2 or rows.shape[0] != B or tuple(nrows.shape) != (B,) or tuple(gy_rows.shape) != (B, rows.shape[1], Cout):
+            raise _lib.HouvHipError(f"mlp2_max_backward: expected rows[{B},R], nrows[{B}], gy_rows[{B},R,{Cout}], got "
+                                    f"{tuple(rows.shape)}, {tuple(nrows.shape)}, {tuple(gy_rows.shape)}")
+        R = rows.shape[1]
+        if R == 0:
+            rows = nrows = gy_rows = None
+    dev = x.device
+    lib = _lib.load()
+    rcap = lib.houv_mlp2_max_backward_rows(N, Cout, R)
+    out = dict(gW1=torch.empty((H, Cin), dtype=_F32, device=dev), gshift1=torch.empty((B, H), dtype=_F32, device=dev),
+               gW2=torch.empty((Cout, H), dtype=_F32, device=dev), gb2=torch.empty((Cout,), dtype=_F32, device=dev),
+               act_rows=torch.empty((B, rcap), dtype=_I32, device=dev), nact=torch.empty((B,), dtype=_I32, device=dev),
+               gx_rows=torch.empty((B, rcap, Cin), dtype=_F32, device=dev) if want_gx else None)
+    nbytes = lib.houv_mlp2_max_backward_workspace_bytes(B, N, Cin, H, Cout, R)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ok = lib.houv_mlp2_max_backward(_lib.ptr(x), B, N, Cin, _lib.ptr(W1), H, _lib.ptr(shift1), stride, _lib.ptr(W2), Cout,
+                                        _lib.ptr(arg), _lib.ptr(gpooled), _lib.ptr(rows), _lib.ptr(nrows), _lib.ptr(gy_rows), R,
+                                        _lib.ptr(out["gW1"]), _lib.ptr(out["gshift1"]), _lib.ptr(out["gW2"]), _lib.ptr(out["gb2"]),
+                                        _lib.ptr(out["act_rows"]), _lib.ptr(out["nact"]), _lib.ptr(out["gx_rows"]), _lib.ptr(ws),
+                                        _lib.stream_of(x))
+    _lib.check(ok, "houv_mlp2_max_backward")
+    return out
+
+
 def pcn_fold(coarse, cvec, grid, Wgp, W2, b2, W3, b3):
     """The folding stage of PCN_decoder.forward (registration/models/pcn.py:108-125) in one kernel (houv_pcn_fold):
     coarse[B,nc,3], cvec[B,512], grid[2,scale], Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3] -> fine[B,nc*scale,3]."""
@@ -447,6 +537,38 @@ def pcn_fold(coarse, cvec, grid, Wgp, W2, b2, W3, b3):
                                        _lib.ptr(b2), _lib.ptr(W3), _lib.ptr(b3), _lib.ptr(fine), _lib.stream_of(coarse))
     _lib.check(ok, "houv_pcn_fold")
     return fine
+
+
+def pcn_fold_backward(coarse, cvec, grid, Wgp, W2, b2, W3, b3, gfine):
+    """The backward pass of pcn_fold (houv_pcn_fold_backward): pcn_fold's arguments plus
+    gfine[B,nc*scale,3] -> dict(gcoarse[B,nc,3], gcvec[B,512], gWgp[512,5], gW2[512,512], gb2[512], gW3[3,512], gb3[3])."""
+    ts = (coarse, cvec, grid, Wgp, W2, b2, W3, b3, gfine)
+    _lib.require_gpu(*ts)
+    for t in ts:
+        _want(t, _F32, "pcn_fold_backward")
+    if coarse.dim() != 3 or coarse.shape[2] != 3 or grid.dim() != 2 or grid.shape[0] != 2 \
+            or tuple(cvec.shape) != (coarse.shape[0], 512):
+        raise _lib.HouvHipError(f"pcn_fold_backward: expected coarse[B,nc,3], cvec[B,512], grid[2,scale], got {tuple(coarse.shape)}, "
+                                f"{tuple(cvec.shape)}, {tuple(grid.shape)}")
+    if tuple(Wgp.shape) != (512, 5) or tuple(W2.shape) != (512, 512) or b2.numel() != 512 or tuple(W3.shape) != (3, 512) \
+            or b3.numel() != 3:
+        raise _lib.HouvHipError("pcn_fold_backward: expected Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3]")
+    B, nc, _ = coarse.shape
+    scale = grid.shape[1]
+    if tuple(gfine.shape) != (B, nc * scale, 3):
+        raise _lib.HouvHipError(f"pcn_fold_backward: gfine must be [{B},{nc * scale},3], got {tuple(gfine.shape)}")
+    dev = coarse.device
+    new = lambda *shape: torch.empty(shape, dtype=_F32, device=dev)
+    out = dict(gcoarse=new(B, nc, 3), gcvec=new(B, 512), gWgp=new(512, 5), gW2=new(512, 512), gb2=new(512), gW3=new(3, 512), gb3=new(3))
+    lib = _lib.load()
+    nbytes = lib.houv_pcn_fold_backward_workspace_bytes(B, nc, scale)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ok = lib.houv_pcn_fold_backward(*(_lib.ptr(t) for t in ts[:3]), B, nc, scale, *(_lib.ptr(t) for t in ts[3:]),
+                                        *(_lib.ptr(out[k]) for k in ("gcoarse", "gcvec", "gWgp", "gW2", "gb2", "gW3", "gb3")),
+                                        _lib.ptr(ws), nbytes, _lib.stream_of(coarse))
+    _lib.check(ok, "houv_pcn_fold_backward")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -585,7 +707,12 @@ def register_torch_ops():
                "Tensor W3, Tensor s3, Tensor t3, Tensor w4, Tensor b4) -> (Tensor, Tensor, Tensor, Tensor)")
     lib.define("edge_diff(Tensor x, Tensor idx, int k, int ldo) -> Tensor")
     lib.define("mlp2_max(Tensor x, Tensor W1, Tensor shift1, Tensor W2, Tensor b2) -> (Tensor, Tensor)")
+    lib.define("mlp2_max_arg(Tensor x, Tensor W1, Tensor shift1, Tensor W2, Tensor b2) -> (Tensor, Tensor, Tensor)")
+    lib.define("mlp2_max_backward(Tensor x, Tensor W1, Tensor shift1, Tensor W2, Tensor arg, Tensor gpooled, Tensor? rows, "
+               "Tensor? nrows, Tensor? gy_rows) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
     lib.define("pcn_fold(Tensor coarse, Tensor cvec, Tensor grid, Tensor Wgp, Tensor W2, Tensor b2, Tensor W3, Tensor b3) -> Tensor")
+    lib.define("pcn_fold_backward(Tensor coarse, Tensor cvec, Tensor grid, Tensor Wgp, Tensor W2, Tensor b2, Tensor W3, Tensor b3, "
+               "Tensor gfine) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
     lib.define("knn_feat(Tensor x, int k) -> (Tensor, Tensor)")
     lib.define("dense_conv(Tensor x, Tensor idx, Tensor W0, Tensor b0, Tensor W1, Tensor b1, Tensor W2, Tensor b2, "
                "bool relu_out) -> Tensor")
@@ -625,7 +752,21 @@ def register_torch_ops():
     def _mlp2_max(*a):
         return mlp2_max(*a, want_y=True)
     lib.impl("mlp2_max", _mlp2_max, "CUDA")
+
+    def _mlp2_max_arg(*a):
+        return mlp2_max_arg(*a, want_y=True)
+    lib.impl("mlp2_max_arg", _mlp2_max_arg, "CUDA")
+
+    def _mlp2_max_backward(*a):
+        r = mlp2_max_backward(*a, want_gx=True)
+        return tuple(r[k] for k in ("gW1", "gshift1", "gW2", "gb2", "act_rows", "nact", "gx_rows"))
+    lib.impl("mlp2_max_backward", _mlp2_max_backward, "CUDA")
     lib.impl("pcn_fold", pcn_fold, "CUDA")
+
+    def _pcn_fold_backward(*a):
+        r = pcn_fold_backward(*a)
+        return tuple(r[k] for k in ("gcoarse", "gcvec", "gWgp", "gW2", "gb2", "gW3", "gb3"))
+    lib.impl("pcn_fold_backward", _pcn_fold_backward, "CUDA")
 
     def _knn_feat(x, k):
         return knn_feat(x, k, want_dist=True)

@@ -426,6 +426,45 @@ int houv_mlp2_max(const float* x, int B, int N, int Cin, const float* W1, int H,
                   const float* W2, const float* b2, int Cout, float* pooled, float* y_or_null, float* workspace, void* stream);
 long long houv_mlp2_max_workspace_bytes(int B, int N, int Cout);
 
+/* houv_mlp2_max that also reports where each maximum was found: the arguments, checks and served
+ * shapes of houv_mlp2_max plus arg[B,Cout].  pooled and y are bit-identical to houv_mlp2_max's.
+ *   arg[b,c] = the LOWEST n with y[b,n,c] == pooled[b,c]   (float equality; the rule of torch.max(x, 2) on the CPU, where a
+ *              tied maximum returns its first index and receives the whole gradient)
+ * A column that is NaN in every row has no such n: arg = -1 (its pooled is -inf, as above), and a backward pass sends no
+ * gradient through it.  A column whose largest value is a true -inf reports the first row holding it.  The per-tile
+ * (maximum, row) pairs pass through `workspace` (houv_mlp2_max_arg_workspace_bytes(B, N, Cout) bytes, twice the plain call's;
+ * may be NULL when that is 0); the first tile that attains the maximum keeps it. */
+int houv_mlp2_max_arg(const float* x, int B, int N, int Cin, const float* W1, int H, const float* shift1,
+                      long long shift1_stride, const float* W2, const float* b2, int Cout, float* pooled, int32_t* arg,
+                      float* y_or_null, float* workspace, void* stream);
+long long houv_mlp2_max_arg_workspace_bytes(int B, int N, int Cout);
+
+/* The backward pass of one PointNet block, evaluated on the ACTIVE rows only.  With
+ *   h = relu(W1 x + shift1[b]),  z = W2 h + b2,  pooled = max over n of z   (houv_mlp2_max_arg gave arg)
+ * the gradient of pooled[b,c] reaches row arg[b,c] alone (arg < 0 or >= N: no row, no gradient).  A gradient on y itself may
+ * come along on a list of rows per cloud: rows[B,R] (STRICTLY ascending in each cloud's first nrows[b] <= R entries, the
+ * rest ignored), gy_rows[B,R,Cout] (the gradient of y[b, rows[b,k], :]); R = 0 with NULL for the three: no such gradient.
+ * Let A_b = set(arg[b,:]) u rows[b]; it has at most Rcap = houv_mlp2_max_backward_rows(N, Cout, R) = min(N, Cout + R) rows.
+ *   gz[b,r,c] = gy[b,r,c] + gpooled[b,c] * [arg[b,c] == r]            for r in A_b (never stored)
+ *   gb2[Cout] = sum gz;   gW2[Cout,H] = sum gz^T h;   gh = (gz W2) * [h > 0];   gW1[H,Cin] = sum gh^T x
+ *   gshift1[B,H] = sum over r in A_b of gh   (always one row per cloud: the caller sums it when shift1 was shared)
+ *   gx = gh W1
+ * Row-carried outputs are COMPACTED per cloud: act_rows[B,Rcap] holds A_b ascending and -1 in the slots past nact[b] =
+ * |A_b|; gx_rows_or_null[B,Rcap,Cin] holds gx of row act_rows[b,p] in slot p and exact zeros in the slots past nact[b].
+ * (act_rows, nact, gx_rows) of the block that consumed y is therefore (rows, nrows, gy_rows) of the block that made it.
+ * h is recomputed on the active rows by houv_gemm_f32, whose rounding may differ from the forward's in the last place: a
+ * hidden unit within that of zero may be masked differently.  Sums run clouds ascending, rows ascending; no atomics; two
+ * calls give the same bits.  x, W1, shift1 (+ stride), W2 as in houv_mlp2_max, same served shapes; R >= 0; B <= 65535
+ * (B = 0 writes zero weight gradients).  workspace: houv_mlp2_max_backward_workspace_bytes(B, N, Cin, H, Cout, R) bytes,
+ * 16-byte aligned, caller-allocated. */
+int houv_mlp2_max_backward(const float* x, int B, int N, int Cin, const float* W1, int H, const float* shift1,
+                           long long shift1_stride, const float* W2, int Cout, const int32_t* arg, const float* gpooled,
+                           const int32_t* rows_or_null, const int32_t* nrows_or_null, const float* gy_rows_or_null, int R,
+                           float* gW1, float* gshift1, float* gW2, float* gb2, int32_t* act_rows, int32_t* nact,
+                           float* gx_rows_or_null, void* workspace, void* stream);
+long long houv_mlp2_max_backward_workspace_bytes(int B, int N, int Cin, int H, int Cout, int R);
+int houv_mlp2_max_backward_rows(int N, int Cout, int R);
+
 /* The folding stage of PCN_decoder.forward (pcn.py:108-125).  coarse[B,nc,3], cvec[B,512] (the global feature's share of the
  * first convolution plus its bias, one vector per cloud), grid[2,scale], Wgp[512,5] (the first convolution's columns for the
  * two grid and three centre channels), W2[512,512], b2[512], W3[3,512], b3[3]; nc, scale >= 1.  For fine point f = c*scale + s:
@@ -435,6 +474,23 @@ long long houv_mlp2_max_workspace_bytes(int B, int N, int Cout);
  * fine[B, nc*scale, 3] is the only tensor written. */
 int houv_pcn_fold(const float* coarse, const float* cvec, const float* grid, int B, int nc, int scale, const float* Wgp,
                   const float* W2, const float* b2, const float* W3, const float* b3, float* fine, void* stream);
+
+/* The backward pass of houv_pcn_fold: its inputs plus gfine[B, nc*scale, 3], the gradient of fine.
+ *   gh2 = (W3^T gfine) * [h2 > 0];  gh1 = (gh2 W2) * [h1 > 0]   per fine point, h1 and h2 recomputed as the forward computes them
+ *   gW3[3,512] = sum gfine^T h2;  gb3[3] = sum gfine;  gW2[512,512] = sum gh2^T h1;  gb2[512] = sum gh2
+ *   gWgp[512,5] = sum gh1^T (grid[0,s], grid[1,s], coarse[b,c,:]);  gcvec[B,512] = sum over the cloud's fine points of gh1
+ *   gcoarse[B,nc,3] = sum over the scale cells s ascending of (gfine[b, c*scale+s, :] + gh1 Wgp[:, 2:5]): the centre path and
+ *                     the path through the first convolution
+ * (b3 is checked but not read.)  The forward saved nothing.  Row sums leave the kernel as per-tile partials that are added in
+ * tile order, gW2 is a houv_gemm_f32 over row chunks whose partials are added in chunk order: no atomics, two calls give the
+ * same bits.  workspace: houv_pcn_fold_backward_workspace_bytes(B, nc, scale) bytes, 16-byte aligned, caller-allocated (h1 and
+ * the k-major gh2 of every fine point, the partials); `workspace_bytes` is what the caller allocated, and a smaller or NULL
+ * workspace is refused.  B = 0 writes zero weight gradients. */
+int houv_pcn_fold_backward(const float* coarse, const float* cvec, const float* grid, int B, int nc, int scale, const float* Wgp,
+                           const float* W2, const float* b2, const float* W3, const float* b3, const float* gfine,
+                           float* gcoarse, float* gcvec, float* gWgp, float* gW2, float* gb2, float* gW3, float* gb3,
+                           void* workspace, long long workspace_bytes, void* stream);
+long long houv_pcn_fold_backward_workspace_bytes(int B, int nc, int scale);
 
 /* ---------------------------------------------------------------------------------------------
  * ECG completion network (completion/models/ecg.py).  fp32 data, fixed expression trees, no allocation,
