@@ -80,6 +80,10 @@ _SIGNATURES = {
     "houv_pcn_fold_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
     "houv_knn_feat": (ctypes.c_int, [_c_f, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
     "houv_dense_conv": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 6 + [_int, _c_f, _int, _c_f]),
+    "houv_dense_conv_arg": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 6 + [_int, _c_f, _int, _c_f, _c_f]),
+    "houv_dense_conv_backward": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 6 +
+                                 [_int, _c_f, _c_f, _int, _c_f, _int, _c_f, _int] + [_c_f] * 7 + [ctypes.c_longlong, _c_f]),
+    "houv_dense_conv_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int, _int]),
     "houv_sa_attn": (ctypes.c_int, [_c_f, _int, _c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 5 + [_int, _c_f, _int, _c_f]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }

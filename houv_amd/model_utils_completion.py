@@ -185,6 +185,89 @@ def three_nn_upsampling(target_points, source_points):
     return idx, inv / inv.sum(dim=2, keepdim=True)
 
 
+def _transposed(a):
+    """a[m,n] -> a fresh, densely packed [n,m].  Not ``a.t().contiguous()``: with m == 1 torch already calls the transposed view
+    contiguous and returns it as it is, with a last stride of n, which the GEMM (unit last stride) refuses -- a batch of one
+    cloud would not train."""
+    out = torch.empty((a.shape[1], a.shape[0]), dtype=a.dtype, device=a.device)
+    out.copy_(a.t())
+    return out
+
+
+class _LinearFunction(torch.autograd.Function):
+    """relu?(x W^T + b) over ops.gemm, with its backward over ops.gemm: gx = gz W, gW = gz^T x, gb = sum gz, gz = gy * [y > 0].
+    x[M,K] and W[N,K] may be column slices of wider row-major buffers (a weight's columns: its gradient then returns through
+    the slice); b may be None.  Shared by the trainable paths of models/pcn.py and models/ecg.py."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, relu):
+        y = ops.gemm(x, W, shift=b, relu=relu)
+        ctx.relu, ctx.bias = relu, b is not None
+        ctx.save_for_backward(x, W, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, W, y = ctx.saved_tensors
+        gz = (gy * (y > 0)).contiguous() if ctx.relu else gy.contiguous()
+        return ops.gemm(gz, W, trans_b=False), ops.gemm(_transposed(gz), _transposed(x)), gz.sum(0) if ctx.bias else None, None
+
+
+class _LinearRowsFunction(_LinearFunction):
+    """_LinearFunction for layers applied to every point of a batch (models/ecg.py): the same forward; the weight gradient's
+    sum over the rows is split into chunks (_weight_grad) and gx is left out when x needs none."""
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, W, y = ctx.saved_tensors
+        gz = (gy * (y > 0)).contiguous() if ctx.relu else gy.contiguous()
+        gx = ops.gemm(gz, W, trans_b=False) if ctx.needs_input_grad[0] else None
+        return gx, _weight_grad(gz, x), gz.sum(0) if ctx.bias else None, None
+
+
+def _weight_grad(gz, x):
+    """gz[M,N]^T x[M,K] -> [N,K].  The output is small and the reduction runs over the M rows: with many rows (every point of a
+    batch) one GEMM would keep a handful of workgroups busy for the whole sum, so the rows are split into S equal chunks (a
+    power of two, chunks of at least 512 rows), one batched GEMM writes S partial products, and they are added in chunk order.
+    A fixed shape gives a fixed order: the same bits from call to call.  Few rows: one GEMM."""
+    gzT, xT = _transposed(gz), _transposed(x)
+    M = gz.shape[0]
+    S = 1
+    while S < 64 and M % (2 * S) == 0 and M // (2 * S) >= 512:
+        S *= 2
+    if S == 1:
+        return ops.gemm(gzT, xT)
+    Mc = M // S
+    part = ops.gemm(gzT.view(-1, S, Mc).transpose(0, 1), xT.view(-1, S, Mc).transpose(0, 1))      # [S,N,K]
+    return part.sum(0)
+
+
+class _RowGather(torch.autograd.Function):
+    """_take_rows with an ordered gradient: rows (B,N,C), idx (B,...) int -> (B,...,C) = rows[b, idx[b,...]].  The backward is
+    houv_scatter_points_grad's sum in ascending order of the flattened idx (no float atomics, unlike torch.gather's)."""
+
+    @staticmethod
+    def forward(ctx, rows, idx):
+        ctx.save_for_backward(idx)
+        ctx.N = rows.shape[1]
+        return _take_rows(rows, idx)
+
+    @staticmethod
+    def backward(ctx, grad):
+        from .mm3d_pn2 import _scatter_grad
+        idx, = ctx.saved_tensors
+        B, C = grad.shape[0], grad.shape[-1]
+        g = _transposed_batch(grad.reshape(B, -1, C))
+        return _transposed_batch(_scatter_grad(g, idx.reshape(B, -1).int().contiguous(), None, ctx.N, 1)), None
+
+
+def _transposed_batch(a):
+    """a[B,m,n] -> a fresh, densely packed [B,n,m] (see _transposed for why not .transpose().contiguous())."""
+    out = torch.empty((a.shape[0], a.shape[2], a.shape[1]), dtype=a.dtype, device=a.device)
+    out.copy_(a.transpose(1, 2))
+    return out
+
+
 def _take_rows(rows, idx):
     """rows (B,N,C) (any row stride), idx (B,...) -> (B,...,C) = rows[b, idx[b,...]]."""
     B, _, C = rows.shape

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..model_utils_completion import calc_cd, calc_emd, gen_grid_up
+from ..model_utils_completion import _LinearFunction, _transposed, calc_cd, calc_emd, gen_grid_up
 
 
 class _Conv1x1(nn.Module):
@@ -44,15 +44,6 @@ class _Conv1x1(nn.Module):
         if cache.get((lo, hi), (None, None))[0] != stamp:
             cache[(lo, hi)] = (stamp, self.matrix()[:, lo:hi].contiguous())
         return cache[(lo, hi)][1]
-
-
-def _transposed(a):
-    """a[m,n] -> a fresh, densely packed [n,m].  Not ``a.t().contiguous()``: with m == 1 torch already calls the transposed view
-    contiguous and returns it as it is, with a last stride of n, which the GEMM (unit last stride) refuses -- a batch of one
-    cloud would not train."""
-    out = torch.empty((a.shape[1], a.shape[0]), dtype=a.dtype, device=a.device)
-    out.copy_(a.t())
-    return out
 
 
 def _linear(layer, x, relu=False):
@@ -116,23 +107,6 @@ class PCN_encoder(nn.Module):
         shift1 = ops.gemm(g1, W3[:, 256:], shift=self.conv3.bias)               # the pooled half of cat(y, g1): once per cloud
         feat, _ = ops.mlp2_max(y, self.conv3.columns(0, 256), shift1, self.conv4.matrix(), self.conv4.bias)
         return feat
-
-
-class _LinearFunction(torch.autograd.Function):
-    """relu?(x W^T + b) over ops.gemm, with its backward over ops.gemm: gx = gz W, gW = gz^T x, gb = sum gz, gz = gy * [y > 0]."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, relu):
-        y = ops.gemm(x, W, shift=b, relu=relu)
-        ctx.relu = relu
-        ctx.save_for_backward(x, W, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, W, y = ctx.saved_tensors
-        gz = (gy * (y > 0)).contiguous() if ctx.relu else gy.contiguous()
-        return ops.gemm(gz, W, trans_b=False), ops.gemm(_transposed(gz), _transposed(x)), gz.sum(0), None
 
 
 class _FoldFunction(torch.autograd.Function):

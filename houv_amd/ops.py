@@ -629,6 +629,85 @@ def dense_conv(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
     return out
 
 
+def _dense_conv_args(who, x, idx, W0, b0, W1, b1, W2, b2):
+    _lib.require_gpu_any(x, W0, b0, W1, b1, W2, b2)
+    _lib.require_gpu(idx, W0, b0, W1, b1, W2, b2); _want(idx, _I32, f"{who}: idx")
+    B, N, C, ldx = _rows(x, f"{who}: x")
+    G = DENSE_CONV_GROWTH
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.HouvHipError(f"{who}: expected idx[{B},{N},k], got {tuple(idx.shape)}")
+    if tuple(W0.shape) != (G, 2 * C) or tuple(W1.shape) != (G, G + C) or tuple(W2.shape) != (G, 2 * G + C) \
+            or b0.numel() != G or b1.numel() != G or b2.numel() != G:
+        raise _lib.HouvHipError(f"{who}: expected W0[24,{2 * C}], W1[24,{G + C}], W2[24,{2 * G + C}] and biases [24], got "
+                                f"{tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
+    return B, N, C, ldx
+
+
+def dense_conv_arg(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
+    """dense_conv that also says where each maximum sits (houv_dense_conv_arg): the same arguments ->
+    (out[B,N,C+72], arg[B,N,72] int8).  out carries dense_conv's bits; arg[b,i,q] is the lowest edge slot whose candidate attains
+    the maximum of pooled column q (y0, s1, s2: 24 each; torch.max's rule on the CPU), -1 for a column that is NaN for every
+    neighbour."""
+    B, N, C, ldx = _dense_conv_args("dense_conv_arg", x, idx, W0, b0, W1, b1, W2, b2)
+    G = DENSE_CONV_GROWTH
+    if out is None:
+        out = torch.empty((B, N, C + 3 * G), dtype=_F32, device=x.device)
+    _lib.require_gpu_any(x, out)
+    if tuple(out.shape) != (B, N, C + 3 * G):
+        raise _lib.HouvHipError(f"dense_conv_arg: out must be [{B},{N},{C + 3 * G}], got {tuple(out.shape)}")
+    ldo = _rows(out, "dense_conv_arg: out")[3]
+    arg = torch.empty((B, N, 3 * G), dtype=torch.int8, device=x.device)
+    with torch.cuda.device(x.device):
+        ok = _lib.load().houv_dense_conv_arg(ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, idx.shape[2], _lib.ptr(W0), _lib.ptr(b0),
+                                             _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), int(bool(relu_out)),
+                                             ctypes_ptr(out), ldo, _lib.ptr(arg), _lib.stream_of(x))
+    _lib.check(ok, "houv_dense_conv_arg")
+    return out, arg
+
+
+def dense_conv_backward(x, idx, W0, b0, W1, b1, W2, b2, arg, gout, out=None, relu_out=False, gx=None):
+    """The backward pass of dense_conv (houv_dense_conv_backward): dense_conv's arguments, arg[B,N,72]
+    int8 from dense_conv_arg, gout[B,N,C+72] (the gradient of out; rows of any stride) and, when relu_out, the forward's out ->
+    dict(gx[B,N,C], gW0[24,2C], gb0[24], gW1[24,24+C], gb1[24], gW2[24,48+C], gb2[24]).  `gx` may be a [B,N,C] column slice of a
+    wider row-major buffer; its other columns are left alone.  Deterministic: no float atomics, fixed sum orders."""
+    B, N, C, ldx = _dense_conv_args("dense_conv_backward", x, idx, W0, b0, W1, b1, W2, b2)
+    G = DENSE_CONV_GROWTH
+    _lib.require_gpu(arg)
+    _lib.require_gpu_any(x, gout, out, gx)
+    if arg.dtype != torch.int8 or tuple(arg.shape) != (B, N, 3 * G):
+        raise _lib.HouvHipError(f"dense_conv_backward: arg must be int8 [{B},{N},{3 * G}], got {arg.dtype} {tuple(arg.shape)}")
+    if tuple(gout.shape) != (B, N, C + 3 * G):
+        raise _lib.HouvHipError(f"dense_conv_backward: gout must be [{B},{N},{C + 3 * G}], got {tuple(gout.shape)}")
+    ldg = _rows(gout, "dense_conv_backward: gout")[3]
+    ldo = 0
+    if relu_out:
+        if out is None or tuple(out.shape) != (B, N, C + 3 * G):
+            raise _lib.HouvHipError(f"dense_conv_backward: relu_out needs the forward's out [{B},{N},{C + 3 * G}]")
+        ldo = _rows(out, "dense_conv_backward: out")[3]
+    else:
+        out = None
+    dev = x.device
+    if gx is None:
+        gx = torch.empty((B, N, C), dtype=_F32, device=dev)
+    if tuple(gx.shape) != (B, N, C):
+        raise _lib.HouvHipError(f"dense_conv_backward: gx must be [{B},{N},{C}], got {tuple(gx.shape)}")
+    ldgx = _rows(gx, "dense_conv_backward: gx")[3]
+    new = lambda *shape: torch.empty(shape, dtype=_F32, device=dev)
+    res = dict(gx=gx, gW0=new(G, 2 * C), gb0=new(G), gW1=new(G, G + C), gb1=new(G), gW2=new(G, 2 * G + C), gb2=new(G))
+    lib = _lib.load()
+    k = idx.shape[2]
+    nbytes = lib.houv_dense_conv_backward_workspace_bytes(B, N, C, k)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ok = lib.houv_dense_conv_backward(ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, k, _lib.ptr(W0), _lib.ptr(b0), _lib.ptr(W1),
+                                          _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), int(bool(relu_out)), _lib.ptr(arg),
+                                          ctypes_ptr(out) if out is not None else None, ldo, ctypes_ptr(gout), ldg,
+                                          ctypes_ptr(gx), ldgx, *(_lib.ptr(res[n]) for n in ("gW0", "gb0", "gW1", "gb1", "gW2", "gb2")),
+                                          _lib.ptr(ws), nbytes, _lib.stream_of(x))
+    _lib.check(ok, "houv_dense_conv_backward")
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------
 # VRCNet completion network (houv_sa_attn; DESIGN.md section 9.11)
 # ---------------------------------------------------------------------------------------------------

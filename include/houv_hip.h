@@ -530,6 +530,46 @@ int houv_dense_conv(const float* x, int ldx, const int32_t* idx, int B, int N, i
                     const float* W1, const float* b1, const float* W2, const float* b2, int relu_out, float* out, int ldo,
                     void* stream);
 
+/* houv_dense_conv that also reports where each maximum was found: the arguments, checks and served
+ * shapes of houv_dense_conv plus arg[B,N,72] (int8, 4-byte aligned; the pooled columns in the order y0 (24), s1 (24), s2 (24)).
+ * `out` is written by houv_dense_conv's own kernels and is bit-identical to its result.  A second pass, a kernel of its own,
+ * recomputes the three layers by the same chains and keeps
+ *   arg[b,i,q] = the LOWEST edge slot e in 0 .. k-1 whose candidate attains the maximum of pooled column q   (torch.max's rule
+ *                on the CPU: a tied maximum returns its first index and receives the whole gradient)
+ * A column that is NaN for every neighbour has no such e: arg = -1 (it pools to -inf, as above), and a backward pass sends no
+ * gradient through it.  A column whose largest candidate is a true -inf reports the first slot holding it. */
+int houv_dense_conv_arg(const float* x, int ldx, const int32_t* idx, int B, int N, int C, int k, const float* W0, const float* b0,
+                        const float* W1, const float* b1, const float* W2, const float* b2, int relu_out, float* out, int ldo,
+                        int8_t* arg, void* stream);
+
+/* The backward pass of houv_dense_conv: its inputs, arg from houv_dense_conv_arg, the forward's out
+ * (rows of stride ldo; read only when relu_out is set, NULL allowed otherwise) and gout[B,N,C+72] (rows of stride ldg >= C + 72),
+ * the gradient of out.  With g = gout * [out > 0] when relu_out is set and g = gout otherwise, point i, edge slot e,
+ * j = clamp(idx[i,e], 0, N-1), y0 and s1 recomputed by the forward's own fma chains (the ReLU masks are the forward's bits):
+ *   gs2[o] = g[2G+C+o] * [arg[2G+o] == e]
+ *   gs1[c] = ((sum_o W2[o,G+C+c] gs2[o]) + g[G+C+c] * [arg[G+c] == e]) * [s1[c] > 0]
+ *   gy0[c] = (((sum_o W1[o,c] gs1[o]) + (sum_o W2[o,c] gs2[o])) + g[c] * [arg[c] == e]) * [y0[c] > 0]      sums o ascending, fma
+ * and per point Gy0 = sum_e gy0 (e ascending), Gs1 = sum_e gs1, Gs2[o] = g[2G+C+o] * [arg[2G+o] >= 0],
+ * D[m] = the sum of gy0 over the edges (i, e) with j == m in ascending (i, e) order (the neighbour path lands on the CLAMPED row):
+ *   gx[b,i,c] = (((P1 + P2) + P3) + P4) + g[G+c]   (the pass-through columns last), each P an fma chain from 0, o ascending:
+ *               P1 = sum_o W1[o,G+c] Gs1[o],  P2 = sum_o W2[o,G+c] Gs2[o],  P3 = sum_o W0[o,c] Gy0[o],
+ *               P4 = sum_o W0[o,C+c] (D[i][o] - Gy0[o])
+ *   gW0[G,2C] = sum (Gy0 (x) x_i | gy0 (x) (x_j - x_i));   gW1[G,G+C] = sum (gs1 (x) y0 | Gs1 (x) x_i)
+ *   gW2[G,2G+C] = sum (gs2 (x) y0 | Gs2 (x) x_i | gs2 (x) s1);   gb0, gb1, gb2[G] = sum Gy0, Gs1, Gs2
+ * Every output is written, not accumulated: gx rows have stride ldgx >= C (columns C .. ldgx-1 are not touched).  Weight
+ * gradients are reduced inside each workgroup of 128 points (edges ascending, points ascending), leave as one row of partials
+ * per workgroup and are added in workgroup order; D is houv_scatter_points_grad's ordered sum.  No float atomics: two calls give
+ * the same bits.  The only tensor with a [B,N,k,.] shape is gy0[B,24,N*k] in the workspace.  Served shapes and refusals are
+ * houv_dense_conv's (N * k < 2^31 besides); B = 0 writes zero weight gradients.  workspace:
+ * houv_dense_conv_backward_workspace_bytes(B, N, C, k) bytes (0 for arguments out of range), 16-byte aligned, caller-allocated;
+ * `workspace_bytes` is what the caller allocated, and a smaller or NULL workspace is refused. */
+int houv_dense_conv_backward(const float* x, int ldx, const int32_t* idx, int B, int N, int C, int k, const float* W0,
+                             const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, int relu_out,
+                             const int8_t* arg, const float* out_or_null, int ldo, const float* gout, int ldg, float* gx, int ldgx,
+                             float* gW0, float* gb0, float* gW1, float* gb1, float* gW2, float* gb2, void* workspace,
+                             long long workspace_bytes, void* stream);
+long long houv_dense_conv_backward_workspace_bytes(int B, int N, int C, int k);
+
 /* ---------------------------------------------------------------------------------------------
  * VRCNet completion network (completion/models/vrcnet.py).  The same promises as the ECG block above. */
 
