@@ -85,6 +85,9 @@ _SIGNATURES = {
                                  [_int, _c_f, _c_f, _int, _c_f, _int, _c_f, _int] + [_c_f] * 7 + [ctypes.c_longlong, _c_f]),
     "houv_dense_conv_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int, _int]),
     "houv_sa_attn": (ctypes.c_int, [_c_f, _int, _c_f, _int, _c_f, _int, _int, _int, _int] + [_c_f] * 5 + [_int, _c_f, _int, _c_f]),
+    "houv_sa_attn_backward": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _int, _c_f, _int, _c_f, _int,
+                                             _c_f, _c_f, _c_f, _c_f, ctypes.c_longlong, _c_f]),
+    "houv_sa_attn_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int, _int]),
     "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

@@ -20,6 +20,10 @@ void set_error(const char* fmt, ...);
 // with the error set, 1 when there is nothing to do (P == 0), 2 when `a` may be launched.  Internal: not part of the C ABI.
 struct SolveCommon;
 __attribute__((visibility("hidden"))) int solve_check_args(const char* who, const SolveCommon& a, int use_views);
+// The index step of the ordered scatter (defined in pointops_group.hip): a stable counting sort of keys[B][M] (each in [0, N)) by
+// destination, giving the CSR inverse offsets[B][N+1], order[B][M] with the sources of a destination in ascending m.  Internal.
+__attribute__((visibility("hidden"))) bool scatter_index_launch(const int* keys, int B, int N, int M, int* offsets, int* order,
+                                                                hipStream_t stream);
 inline bool check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

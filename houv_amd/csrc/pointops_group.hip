@@ -219,6 +219,12 @@ unsigned grid_for(size_t total) {
 }
 
 }  // namespace
+
+bool scatter_index_launch(const int* keys, int B, int N, int M, int* offsets, int* order, hipStream_t stream) {
+  scatter_index_kernel<<<B, kScatThreads, 0, stream>>>(keys, N, M, offsets, order);
+  return check_launch("scatter_index_kernel");
+}
+
 }  // namespace houv
 
 extern "C" int houv_ball_query(const float* xyz, const float* center, int B, int N, int Mc, float min_radius, float max_radius,

@@ -12,9 +12,10 @@ level.  conv6 sees cat(global, x4) with the global feature constant over the poi
 vector per cloud (the split of EF_encoder.conv5); Folding's [B, 1024 + 64 + 2, num_fine] input is the sum of three such parts.
 
 The module tree and parameter names equal the reference's, so its checkpoints load with ``load_state_dict(strict=True)`` (the
-repository ships no trained weights: tests use seeded ones).  Training is NOT built: the "train" prefix doubles the batch, draws
-two latent samples and needs the KL / MMD terms (the reference's MMD branch also calls a method that does not exist); it raises
-NotImplementedError.
+repository ships no trained weights: tests use seeded ones).  SA_module, SK_SA_module and SKN_Res_unit take trainable=True
+(one _SAAttnFunction node per attention block over houv_sa_attn_backward); the encoder hierarchy, the
+decoder and Model stay inference only: the "train" prefix doubles the batch, draws two latent samples and needs the KL / MMD
+terms (the reference's MMD branch also calls a method that does not exist); it raises NotImplementedError.
 
 Two things the reference does that are easy to miss and are kept: Linear_ResBlock's ReLU is in place, so its residual branch
 sees relu(feature) and the CALLER's tensor is rectified too -- the decoder receives relu(feat) + generator(z), not feat +
@@ -31,7 +32,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..mm3d_pn2 import furthest_point_sample, knn_cross
-from ..model_utils_completion import Conv1x1, EF_expansion, _take_rows, calc_cd, calc_emd, gen_grid_up
+from ..model_utils_completion import (Conv1x1, EF_expansion, _LinearFunction, _LinearRowsFunction, _take_rows, _weight_grad, calc_cd,
+                                       calc_emd, gen_grid_up)
 from .ecg import EF_encoder
 from .pcn import PCN_encoder
 
@@ -64,12 +66,50 @@ def _knn_rows(pts, k):
     return knn_cross(k, pts, pts)[1]
 
 
+def _builds_graph(module, out):
+    """True when a module built with trainable=True is called with grad mode on: its forward then keeps a graph.  Everything else
+    runs without one, exactly as before."""
+    if not (module.trainable and torch.is_grad_enabled()):
+        return False
+    if out is not None:
+        raise ValueError(f"{type(module).__name__}: `out` is not served with trainable=True under grad mode (the result is a node "
+                         "of the graph, not a slice of the caller's buffer)")
+    return True
+
+
+class _SAAttnFunction(torch.autograd.Function):
+    """SA_module after its input projections as ONE autograd node: ops.sa_attn forward (the inference
+    path's own call, so the output carries its bits; `out` is never `x`), and backward = the outer mask, G = gy . Wout on the
+    matrix pipe, houv_sa_attn_backward, gWout = gy^T . relu(o) and gbout = sum gy.  Saved: P, idx, the four weight matrices that
+    the backward reads and, when relu_out, the output (for its mask).  idx is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, P, x, idx, Ww1, Ww2, bw2, Wout, bout, relu_out):
+        out = ops.sa_attn(P, x, idx, Ww1, Ww2, bw2, Wout, bout, relu_out=relu_out)
+        ctx.relu_out = bool(relu_out)
+        ctx.save_for_backward(P, idx, Ww1, Ww2, bw2, Wout, *((out,) if relu_out else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        P, idx, Ww1, Ww2, bw2, Wout = ctx.saved_tensors[:6]
+        gy = (gout * (ctx.saved_tensors[6] > 0)).contiguous() if ctx.relu_out else gout.contiguous()
+        B, N, C = gy.shape
+        gy2 = gy.view(B * N, C)
+        r = ops.sa_attn_backward(P, idx, Ww1, Ww2, bw2, ops.gemm(gy2, Wout, trans_b=False).view(B, N, -1))
+        gWout = _weight_grad(gy2, r["ro"].view(B * N, -1))
+        return r["gP"], gy, None, r["gWw1"], r["gWw2"], r["gbw2"], gWout, gy2.sum(0), None
+
+
 class SA_module(nn.Module):
     """vrcnet.py:21-67, the point self-attention block, for what SKN_Res_unit builds: in_planes = out_planes = C in {64, 128, 256,
-    512}, rel_planes = C/16, mid_planes = C/4, share_planes = 8 (houv_sa_attn serves these)."""
+    512}, rel_planes = C/16, mid_planes = C/4, share_planes = 8 (houv_sa_attn serves these).  trainable=True: with grad mode on,
+    forward_rows builds a graph (the projection through _LinearRowsFunction, the rest one _SAAttnFunction node) whose output
+    carries the bits of the inference path; x may require a gradient."""
 
-    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=16):
+    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=16, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         C = in_planes
         if (C not in (64, 128, 256, 512) or out_planes != C or rel_planes != C // 16 or mid_planes != C // 4 or share_planes != 8
                 or not 1 <= k <= 32):
@@ -83,88 +123,113 @@ class SA_module(nn.Module):
                                     nn.ReLU(inplace=False), Conv1x1(mid_planes // share_planes, k * mid_planes // share_planes, 2))
         self.conv_out = Conv1x1(mid_planes, out_planes, 2)
 
-    @torch.no_grad()
     def forward_rows(self, x, idx, relu_out=False, out=None):
         """x (B,N,C) rows (a column slice is fine), idx (B,N,k) int32 -> (B,N,C); relu_out: SK_SA_module's activation."""
         B, N, C = x.shape
         if idx.shape[2] != self.k:
             raise ValueError(f"SA_module: built for k = {self.k}, got lists of {idx.shape[2]}")
-        W = torch.cat((self.conv1.matrix(), self.conv2.matrix(), self.conv3.matrix()), 0)
-        b = torch.cat((self.conv1.bias, self.conv2.bias, self.conv3.bias), 0)
-        P = ops.gemm(torch.relu(x).reshape(-1, C), W, shift=b).view(B, N, -1)
-        return ops.sa_attn(P, x, idx, self.conv_w[1].matrix(), self.conv_w[3].matrix(), self.conv_w[3].bias, self.conv_out.matrix(),
-                           self.conv_out.bias, relu_out=relu_out, out=out)
+        train = _builds_graph(self, out)
+        with torch.set_grad_enabled(train):
+            W = torch.cat((self.conv1.matrix(), self.conv2.matrix(), self.conv3.matrix()), 0)
+            b = torch.cat((self.conv1.bias, self.conv2.bias, self.conv3.bias), 0)
+            w = (self.conv_w[1].matrix(), self.conv_w[3].matrix(), self.conv_w[3].bias, self.conv_out.matrix(), self.conv_out.bias)
+            if train:
+                P = _LinearRowsFunction.apply(torch.relu(x).reshape(-1, C), W, b, False).view(B, N, -1)
+                return _SAAttnFunction.apply(P, x, idx, *w, bool(relu_out))
+            P = ops.gemm(torch.relu(x).reshape(-1, C), W, shift=b).view(B, N, -1)
+            return ops.sa_attn(P, x, idx, *w, relu_out=relu_out, out=out)
 
-    @torch.no_grad()
     def forward(self, input):
         """[x (B,C,1,N), idx (B,N,k)] -> [out (B,C,1,N), idx], the reference's layout."""
         x, idx = input
-        rows = x.squeeze(2).transpose(1, 2).contiguous().float()
-        out = self.forward_rows(rows, idx.int().contiguous())
-        return [out.transpose(1, 2).unsqueeze(2).contiguous(), idx]
+        with torch.set_grad_enabled(_builds_graph(self, None)):
+            rows = x.squeeze(2).transpose(1, 2).contiguous().float()
+            out = self.forward_rows(rows, idx.int().contiguous())
+            return [out.transpose(1, 2).unsqueeze(2).contiguous(), idx]
 
 
 class SK_SA_module(nn.Module):
     """vrcnet.py:130-188: one SA_module per k-NN list, fused by a softmax over the branches.  With one list the softmax is exactly
     1 and the result is relu(SA_module(x)) (fc / fcs exist, for the checkpoint, and are not evaluated)."""
 
-    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=(10, 20), r=2, L=32):
+    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=(10, 20), r=2, L=32, trainable=False):
         super().__init__()
         self.num_kernels = len(k)
+        self.trainable = bool(trainable)
         d = max(int(out_planes / r), L)
-        self.sams = nn.ModuleList([SA_module(in_planes, rel_planes, mid_planes, out_planes, share_planes, ki) for ki in k])
+        self.sams = nn.ModuleList([SA_module(in_planes, rel_planes, mid_planes, out_planes, share_planes, ki, trainable=trainable)
+                                   for ki in k])
         self.fc = nn.Linear(out_planes, d)
         self.fcs = nn.ModuleList([nn.Linear(d, out_planes) for _ in k])
 
-    @torch.no_grad()
     def forward_rows(self, x, idxs, out=None):
         assert self.num_kernels == len(idxs)
-        if self.num_kernels == 1:
-            return self.sams[0].forward_rows(x, idxs[0], relu_out=True, out=out)
-        feas = [sam.forward_rows(x, idx, relu_out=True) for sam, idx in zip(self.sams, idxs)]
-        fea_s = sum(feas[1:], feas[0]).mean(dim=1)                                        # (B,C)
-        fea_z = _linear(self.fc, fea_s)
-        att = torch.softmax(torch.stack([_linear(fc, fea_z) for fc in self.fcs], dim=1), dim=1)        # (B,branches,C)
-        v = feas[0] * att[:, 0].unsqueeze(1)
-        for i in range(1, self.num_kernels):
-            v = v + feas[i] * att[:, i].unsqueeze(1)
-        if out is not None:
-            out.copy_(v)
-            return out
-        return v
+        train = _builds_graph(self, out)
+        with torch.set_grad_enabled(train):
+            if self.num_kernels == 1:
+                return self.sams[0].forward_rows(x, idxs[0], relu_out=True, out=out)
+            # trainable: the same houv_gemm_f32 calls through _LinearFunction; the mean, the softmax and the fusion are torch ops
+            linear = (lambda fc, t: _LinearFunction.apply(t, fc.weight, fc.bias, False)) if train else _linear
+            feas = [sam.forward_rows(x, idx, relu_out=True) for sam, idx in zip(self.sams, idxs)]
+            fea_s = sum(feas[1:], feas[0]).mean(dim=1)                                        # (B,C)
+            fea_z = linear(self.fc, fea_s)
+            att = torch.softmax(torch.stack([linear(fc, fea_z) for fc in self.fcs], dim=1), dim=1)        # (B,branches,C)
+            v = feas[0] * att[:, 0].unsqueeze(1)
+            for i in range(1, self.num_kernels):
+                v = v + feas[i] * att[:, i].unsqueeze(1)
+            if out is not None:
+                out.copy_(v)
+                return out
+            return v
 
-    @torch.no_grad()
     def forward(self, input):
         x, idxs = input
-        rows = x.squeeze(2).transpose(1, 2).contiguous().float()
-        out = self.forward_rows(rows, [i.int().contiguous() for i in idxs])
-        return [out.transpose(1, 2).unsqueeze(2).contiguous(), idxs]
+        with torch.set_grad_enabled(_builds_graph(self, None)):
+            rows = x.squeeze(2).transpose(1, 2).contiguous().float()
+            out = self.forward_rows(rows, [i.int().contiguous() for i in idxs])
+            return [out.transpose(1, 2).unsqueeze(2).contiguous(), idxs]
 
 
 class SKN_Res_unit(nn.Module):
-    """vrcnet.py:191-224: conv2(relu(sam(conv1(feat)))) + conv_res(feat)."""
+    """vrcnet.py:191-224: conv2(relu(sam(conv1(feat)))) + conv_res(feat).
 
-    def __init__(self, input_size, output_size, k=(10, 20), layers=1):
+    self.af on the last SK_SA_module's output is skipped, with trainable=True too: that output is a convex combination of
+    rectified branches (one rectified branch with a single list), so it is >= 0 and relu is the identity on its value.  The
+    gradient is unchanged as well: relu's mask [v > 0] could only drop an element with v == 0, and v == 0 means every branch is
+    at 0 there (the softmax weights are positive), i.e. every branch's pre-activation was at or below zero, so the branch masks
+    [out > 0] of _SAAttnFunction have already dropped that element's gradient on every path it could take."""
+
+    def __init__(self, input_size, output_size, k=(10, 20), layers=1, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.conv1 = _Conv1x1NoBias(input_size, output_size)
-        self.sam = nn.Sequential(*[SK_SA_module(output_size, output_size // 16, output_size // 4, output_size, 8, k)
-                                   for _ in range(int(layers))])
+        self.sam = nn.Sequential(*[SK_SA_module(output_size, output_size // 16, output_size // 4, output_size, 8, k,
+                                                trainable=trainable) for _ in range(int(layers))])
         self.conv2 = _Conv1x1NoBias(output_size, output_size)
         self.conv_res = _Conv1x1NoBias(input_size, output_size)
 
-    @torch.no_grad()
     def forward_rows(self, feat, idxs, out=None, relu_out=False):
         """feat (B,N,input_size) -> (B,N,output_size), written to `out` (a column slice is fine) when given."""
         B, N, _ = feat.shape
-        f2 = _flat(feat)
-        x = ops.gemm(f2, self.conv1.matrix()).view(B, N, -1)
-        for layer in self.sam:
-            x = layer.forward_rows(x, idxs)
-        res = ops.gemm(f2, self.conv_res.matrix())
-        # self.af(x) is the identity here: an SK_SA_module's output is a convex combination of rectified branches
-        y = ops.gemm(x.view(B * N, -1), self.conv2.matrix(), None if out is None else _flat(out), residual=res,
-                     relu=relu_out)
-        return y.view(B, N, -1) if out is None else out
+        train = _builds_graph(self, out)
+        with torch.set_grad_enabled(train):
+            f2 = _flat(feat)
+            if train:
+                x = _LinearRowsFunction.apply(f2, self.conv1.matrix(), None, False).view(B, N, -1)
+                for layer in self.sam:
+                    x = layer.forward_rows(x, idxs)
+                res = _LinearRowsFunction.apply(f2, self.conv_res.matrix(), None, False)
+                # the GEMM's epilogue is (acc + residual), then max(., 0): the same two fp32 operations as these
+                y = _LinearRowsFunction.apply(x.reshape(B * N, -1), self.conv2.matrix(), None, False) + res
+                return (torch.relu(y) if relu_out else y).view(B, N, -1)
+            x = ops.gemm(f2, self.conv1.matrix()).view(B, N, -1)
+            for layer in self.sam:
+                x = layer.forward_rows(x, idxs)
+            res = ops.gemm(f2, self.conv_res.matrix())
+            # self.af(x) is the identity here: an SK_SA_module's output is a convex combination of rectified branches
+            y = ops.gemm(x.view(B * N, -1), self.conv2.matrix(), None if out is None else _flat(out), residual=res,
+                         relu=relu_out)
+            return y.view(B, N, -1) if out is None else out
 
 
 class SA_SKN_Res_encoder(nn.Module):

@@ -749,6 +749,47 @@ def sa_attn(P, x, idx, Ww1, Ww2, bw2, Wout, bout, relu_out=False, out=None):
     return out
 
 
+def sa_attn_backward(P, idx, Ww1, Ww2, bw2, G, gP=None):
+    """The backward pass of sa_attn up to conv_out (houv_sa_attn_backward): sa_attn's P, idx, Ww1, Ww2, bw2
+    and G[B,N,mid], the gradient of relu(o) (the caller's gy . Wout; rows of any stride) -> dict(gP[B,N,2 rel + mid], ro[B,N,mid] =
+    relu(o) recomputed by the forward's chains, gWw1[m, rel (k+1)], gWw2[k m, m], gbw2[k m]).  `gP` may be a column slice of a wider
+    row-major buffer; its other columns are left alone.  conv_out's own gradients (gWout = gy^T . ro, gbout = sum gy) and the
+    residual's are the caller's.  Deterministic: no float atomics, fixed sum orders.  The workspace is allocated here."""
+    _lib.require_gpu_any(P, Ww1, Ww2, bw2, G, gP)
+    _lib.require_gpu(idx, Ww1, Ww2, bw2); _want(idx, _I32, "sa_attn_backward: idx")
+    B, N, wp, ldp = _rows(P, "sa_attn_backward: P")
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.HouvHipError(f"sa_attn_backward: expected idx[{B},{N},k], got {tuple(idx.shape)}")
+    k = idx.shape[2]
+    if wp % 6 != 0 or wp * 8 // 3 not in (64, 128, 256, 512):
+        raise _lib.HouvHipError(f"sa_attn_backward: P has {wp} columns; 2 rel + mid = 24, 48, 96 or 192 (C = 64 .. 512) are served")
+    C = wp * 8 // 3
+    rel, mid, m = C // 16, C // 4, C // 32
+    if tuple(Ww1.shape) != (m, rel * (k + 1)) or tuple(Ww2.shape) != (k * m, m) or bw2.numel() != k * m:
+        raise _lib.HouvHipError(f"sa_attn_backward: expected Ww1[{m},{rel * (k + 1)}], Ww2[{k * m},{m}], bw2[{k * m}], got "
+                                f"{tuple(Ww1.shape)}, {tuple(Ww2.shape)}, {tuple(bw2.shape)}")
+    if tuple(G.shape) != (B, N, mid):
+        raise _lib.HouvHipError(f"sa_attn_backward: G must be [{B},{N},{mid}], got {tuple(G.shape)}")
+    ldg = _rows(G, "sa_attn_backward: G")[3]
+    dev = P.device
+    new = lambda *shape: torch.empty(shape, dtype=_F32, device=dev)
+    if gP is None:
+        gP = new(B, N, wp)
+    if tuple(gP.shape) != (B, N, wp):
+        raise _lib.HouvHipError(f"sa_attn_backward: gP must be [{B},{N},{wp}], got {tuple(gP.shape)}")
+    ldgp = _rows(gP, "sa_attn_backward: gP")[3]
+    res = dict(gP=gP, ro=new(B, N, mid), gWw1=new(m, rel * (k + 1)), gWw2=new(k * m, m), gbw2=new(k * m))
+    lib = _lib.load()
+    nbytes = lib.houv_sa_attn_backward_workspace_bytes(B, N, C, k)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ok = lib.houv_sa_attn_backward(ctypes_ptr(P), ldp, _lib.ptr(idx), B, N, C, k, _lib.ptr(Ww1), _lib.ptr(Ww2), _lib.ptr(bw2),
+                                       ctypes_ptr(G), ldg, ctypes_ptr(gP), ldgp, _lib.ptr(res["ro"]), mid, _lib.ptr(res["gWw1"]),
+                                       _lib.ptr(res["gWw2"]), _lib.ptr(res["gbw2"]), _lib.ptr(ws), nbytes, _lib.stream_of(P))
+    _lib.check(ok, "houv_sa_attn_backward")
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------

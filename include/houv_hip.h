@@ -599,6 +599,33 @@ int houv_sa_attn(const float* P, int ldp, const float* x, int ldx, const int32_t
                  const float* Ww1, const float* Ww2, const float* bw2, const float* Wout, const float* bout, int relu_out,
                  float* out, int ldo, void* stream);
 
+/* The backward pass of houv_sa_attn up to conv_out.  conv_out is two products over all points and stays
+ * with the caller on the matrix pipe: with gy = gout * [out > 0] when relu_out was set and gy = gout otherwise, the caller forms
+ * G[B,N,mid] = gy . Wout (the gradient of relu(o); rows of stride ldg >= mid), gWout = gy^T . ro and gbout = sum gy; the
+ * residual's share of gx is gy itself.  This call takes P, idx, Ww1, Ww2, bw2 as houv_sa_attn does (the same checks, clamping
+ * and alignment), recomputes t, pre, h, w and o by the forward's own fma chains (every ReLU mask is the forward's bits), writes
+ * ro[B,N,mid] = relu(o) (rows of stride ldro >= mid) and, for point i with n_j = clamp(idx[i,j], 0, N-1):
+ *   go[c]      = G[c] * [o[c] > 0]
+ *   gw[c',j]   = sum over c = c' (mod m), ascending, of go[c] x3[n_j][c]                      an fma chain from 0
+ *   gh[q]      = sum over j, then c', of Ww2[c' k + j, q] gw[c',j];    gpre = gh * [pre > 0]
+ *   gt[s]      = [t[s] > 0] * sum over q of Ww1[q,s] gpre[q]
+ *   gbw2[c' k + j] = sum_i gw[c',j];   gWw2[c' k + j, q] = sum_i gw[c',j] h[q];   gWw1[q,s] = sum_i gpre[q] relu(t[s])
+ *   gP[i, r]           = gt_i[r]                                                               the point's own x1 columns
+ *   gP[n, rel + r]     = sum over the edges (i,j) with n_j == n of gt_i[rel + r k + j]
+ *   gP[n, 2 rel + c]   = sum over the same edges of go_i[c] w_i[c mod m, j]                    an fma chain from 0
+ * The edge sums run in ascending (i, j); a clamped index sends its gradient to the clamped row.  The weight gradients are sums
+ * over fixed chunks of consecutive points (ascending inside a chunk), added in chunk order.  No float atomics: two calls give the
+ * same bits.  Every output is written, not accumulated; gP rows have stride ldgp >= 2 rel + mid and columns beyond are not
+ * touched.  Every float buffer of the workspace is per point ([B,N,w] with w <= rel (k+1) + k m + 2 mid); the only arrays with
+ * N k entries per cloud are int32 (the keys and the CSR inverse of idx).  Served shapes and refusals are houv_sa_attn's (N * k <
+ * 2^31 besides); B = 0 writes zero weight gradients.  workspace: houv_sa_attn_backward_workspace_bytes(B, N, C, k) bytes (0 for
+ * arguments out of range), 16-byte aligned, caller-allocated; `workspace_bytes` is what the caller allocated, and a smaller or
+ * NULL workspace is refused. */
+int houv_sa_attn_backward(const float* P, int ldp, const int32_t* idx, int B, int N, int C, int k, const float* Ww1,
+                          const float* Ww2, const float* bw2, const float* G, int ldg, float* gP, int ldgp, float* ro, int ldro,
+                          float* gWw1, float* gWw2, float* gbw2, void* workspace, long long workspace_bytes, void* stream);
+long long houv_sa_attn_backward_workspace_bytes(int B, int N, int C, int k);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
