@@ -213,7 +213,9 @@ __device__ __forceinline__ void select_all(const Smem& sm, const float (&best)[Q
   unsigned key[Q];
 #pragma unroll
   for (int m = 0; m < NMET; ++m) {
-    const int ksel = (m == 0) ? k_full : k_view;     // the view terms take all points in every caller (k_view == count)
+    // The drivers' view terms take all points (N == M, k_view == count: no select below), but houv_solve_iterate also accepts
+    // N != M and k_view < count: the view terms then select like the full metric (tests/test_gpu_solve_select.py runs both).
+    const int ksel = (m == 0) ? k_full : k_view;
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
       valid[k] = pt_index<BLOCK>(k) < count;
