@@ -13,9 +13,11 @@ vector per cloud (the split of EF_encoder.conv5); Folding's [B, 1024 + 64 + 2, n
 
 The module tree and parameter names equal the reference's, so its checkpoints load with ``load_state_dict(strict=True)`` (the
 repository ships no trained weights: tests use seeded ones).  SA_module, SK_SA_module and SKN_Res_unit take trainable=True
-(one _SAAttnFunction node per attention block over houv_sa_attn_backward); the encoder hierarchy, the
-decoder and Model stay inference only: the "train" prefix doubles the batch, draws two latent samples and needs the KL / MMD
-terms (the reference's MMD branch also calls a method that does not exist); it raises NotImplementedError.
+(one _SAAttnFunction node per attention block over houv_sa_attn_backward), and so does
+SA_SKN_Res_encoder (section 9.15: each edge-preserve pooling one _EdgePoolFunction node over houv_edge_pool /
+houv_edge_pool_backward, which the inference path shares); the decoder and Model stay inference only: the "train" prefix
+doubles the batch, draws two latent samples and needs the KL / MMD terms (the reference's MMD branch also calls a method that
+does not exist); it raises NotImplementedError.
 
 Two things the reference does that are easy to miss and are kept: Linear_ResBlock's ReLU is in place, so its residual branch
 sees relu(feature) and the CALLER's tensor is rectified too -- the decoder receives relu(feat) + generator(z), not feat +
@@ -34,7 +36,7 @@ from .. import ops
 from ..mm3d_pn2 import furthest_point_sample, knn_cross
 from ..model_utils_completion import (Conv1x1, EF_expansion, _LinearFunction, _LinearRowsFunction, _take_rows, _weight_grad, calc_cd,
                                        calc_emd, gen_grid_up)
-from .ecg import EF_encoder
+from .ecg import EF_encoder, _conv, _lin
 from .pcn import PCN_encoder
 
 
@@ -99,6 +101,25 @@ class _SAAttnFunction(torch.autograd.Function):
         r = ops.sa_attn_backward(P, idx, Ww1, Ww2, bw2, ops.gemm(gy2, Wout, trans_b=False).view(B, N, -1))
         gWout = _weight_grad(gy2, r["ro"].view(B * N, -1))
         return r["gP"], gy, None, r["gWw1"], r["gWw2"], r["gbw2"], gWout, gy2.sum(0), None
+
+
+class _EdgePoolFunction(torch.autograd.Function):
+    """edge_preserve_sampling's feature half as ONE autograd node: feat (B,N,C), p_idx (B,S), pn_idx
+    (B,S,pk) -> (B,S,2C) = cat(centre rows, neighbour max) by ops.edge_pool, the inference path's own kernel, with the slot of
+    every maximum recorded.  Saved: the two index arrays and the int8 arg -- no feature tensor.  backward =
+    ops.edge_pool_backward, the ordered sum per source row."""
+
+    @staticmethod
+    def forward(ctx, feat, p_idx, pn_idx):
+        out, arg = ops.edge_pool(feat, p_idx, pn_idx, want_arg=True)
+        ctx.N = feat.shape[1]
+        ctx.save_for_backward(p_idx, pn_idx, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        p_idx, pn_idx, arg = ctx.saved_tensors
+        return ops.edge_pool_backward(gout.contiguous(), p_idx, pn_idx, arg, ctx.N), None, None
 
 
 class SA_module(nn.Module):
@@ -234,17 +255,28 @@ class SKN_Res_unit(nn.Module):
 
 class SA_SKN_Res_encoder(nn.Module):
     """vrcnet.py:227-362 on rows: points (B,N,input_size), coordinates in columns 0..2 -> (B,N,output_size).  N must equal
-    pts_num[0] only in so far as the levels below it are sampled to pts_num[1..3] points."""
+    pts_num[0] only in so far as the levels below it are sampled to pts_num[1..3] points.
 
-    def __init__(self, input_size=3, k=(10, 20), pk=16, output_size=64, layers=(2, 2, 2, 2), pts_num=(3072, 1536, 768, 384)):
+    trainable=True: with grad mode on, forward_rows and forward build a graph the way
+    EF_encoder.train_rows does -- the four SKN_Res_units' own graphs, each pooling one _EdgePoolFunction node, the linear layers
+    through _LinearRowsFunction / _LinearFunction, the up-samplings through three_interpolate's ordered gradient, the reference's
+    concatenations as torch.cat of rows, and the reference's two nn.Dropout() after the rectified fc layers as F.dropout(., 0.5,
+    self.training) (no parameters: the state_dict is unchanged).  The lists, samples and interpolation weights come from the
+    detached coordinates and are constants, as in the reference; `points` may carry a gradient, which flows through sam_res1.
+    In eval() the output carries the bits of the inference path.  With grad mode off, or trainable=False, the inference path
+    runs and builds no graph."""
+
+    def __init__(self, input_size=3, k=(10, 20), pk=16, output_size=64, layers=(2, 2, 2, 2), pts_num=(3072, 1536, 768, 384),
+                 trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.init_channel = 64
         c1 = self.init_channel
         c2, c3, c4 = c1 * 2, c1 * 4, c1 * 8
-        self.sam_res1 = SKN_Res_unit(input_size, c1, k, int(layers[0]))
-        self.sam_res2 = SKN_Res_unit(c2, c2, k, int(layers[1]))
-        self.sam_res3 = SKN_Res_unit(c3, c3, k, int(layers[2]))
-        self.sam_res4 = SKN_Res_unit(c4, c4, k, int(layers[3]))
+        self.sam_res1 = SKN_Res_unit(input_size, c1, k, int(layers[0]), trainable=trainable)
+        self.sam_res2 = SKN_Res_unit(c2, c2, k, int(layers[1]), trainable=trainable)
+        self.sam_res3 = SKN_Res_unit(c3, c3, k, int(layers[2]), trainable=trainable)
+        self.sam_res4 = SKN_Res_unit(c4, c4, k, int(layers[3]), trainable=trainable)
         self.conv5 = Conv1x1(c4, 1024, 2)
         self.fc1 = nn.Linear(1024, 512)
         self.fc2 = nn.Linear(512, 1024)
@@ -264,22 +296,53 @@ class SA_SKN_Res_encoder(nn.Module):
                 trace[f"knn{level}_{i}"] = out[-1]
         return out
 
-    def _pool(self, level, feat, pts, trace):
+    def _pool(self, level, feat, pts, trace, train=False):
         """edge_preserve_sampling (model_utils.py:90-116) on rows: feat (B,N,C), pts (B,N,3) -> (cat(centre, neighbour max)
-        (B,S,2C), the sampled points (B,S,3))."""
-        S, C = self.pts_num[level], feat.shape[2]
-        p_idx = furthest_point_sample(pts, S)
-        centres = _take_rows(pts, p_idx).contiguous()
-        pn_idx = knn_cross(int(min(self.pk, pts.shape[1])), centres, pts)[1]
+        (B,S,2C), the sampled points (B,S,3)).  One houv_edge_pool either way; `train`: as a node of the graph.  The sample and
+        the lists are constants."""
+        S = self.pts_num[level]
+        with torch.no_grad():
+            p_idx = furthest_point_sample(pts, S)
+            centres = _take_rows(pts, p_idx).contiguous()
+            pn_idx = knn_cross(int(min(self.pk, pts.shape[1])), centres, pts)[1]
         if trace is not None:
             trace[f"fps{level}"], trace[f"knn_pt{level}"] = p_idx, pn_idx
-        out = torch.empty((feat.shape[0], S, 2 * C), dtype=torch.float32, device=feat.device)
-        out[..., :C] = _take_rows(feat, p_idx)
-        out[..., C:] = _take_rows(feat, pn_idx).amax(dim=2)
-        return out, centres
+        if train:
+            return _EdgePoolFunction.apply(feat, p_idx, pn_idx), centres
+        return ops.edge_pool(feat, p_idx, pn_idx), centres
 
-    @torch.no_grad()
-    def forward_rows(self, points, trace=None):
+    def forward_rows(self, points, trace=None, out=None):
+        """points (B,N,input_size) -> (B,N,output_size), written to `out` when given (the inference path only)."""
+        if _builds_graph(self, out):
+            return self._train_rows(points, trace)
+        with torch.no_grad():
+            return self._infer_rows(points, trace, out)
+
+    def _train_rows(self, points, trace):
+        """forward_rows with a graph: the same calls in the same order, the buffers' column slices as torch.cat of rows."""
+        B = points.shape[0]
+        c4 = self.widths[3]
+        pt1 = points.detach()[..., :3].contiguous()
+        x1 = self.sam_res1.forward_rows(points, self._lists(1, pt1, trace), relu_out=True)
+        f, pt2 = self._pool(1, x1, pt1, trace, train=True)
+        x2 = self.sam_res2.forward_rows(f, self._lists(2, pt2, trace), relu_out=True)
+        f, pt3 = self._pool(2, x2, pt2, trace, train=True)
+        x3 = self.sam_res3.forward_rows(f, self._lists(3, pt3, trace), relu_out=True)
+        f, pt4 = self._pool(3, x3, pt3, trace, train=True)
+        x4 = self.sam_res4.forward_rows(f, self._lists(4, pt4, trace), relu_out=True)
+
+        g = _conv(self.conv5, x4).max(dim=1).values
+        g = F.dropout(_LinearFunction.apply(g, self.fc1.weight, self.fc1.bias, True), 0.5, self.training)
+        g = F.dropout(_LinearFunction.apply(g, self.fc2.weight, self.fc2.bias, True), 0.5, self.training)
+        W6 = self.conv6.matrix()
+        shift = _LinearFunction.apply(g, W6[:, :1024], self.conv6.bias, False)    # the global feature's share of conv6, per cloud
+        y = torch.relu(_lin(x4, W6[:, 1024:], None).view(B, -1, c4) + shift.unsqueeze(1))
+        y = _conv(self.conv7, torch.cat((EF_encoder._upsample_train(1, y, pt3, pt4, trace), x3), dim=2), relu=True)
+        y = _conv(self.conv8, torch.cat((EF_encoder._upsample_train(2, y, pt2, pt3, trace), x2), dim=2), relu=True)
+        y = _conv(self.conv9, torch.cat((EF_encoder._upsample_train(3, y, pt1, pt2, trace), x1), dim=2), relu=True)
+        return _conv(self.conv_out, y)
+
+    def _infer_rows(self, points, trace, out):
         B, N, _ = points.shape
         c1, c2, c3, c4 = self.widths
         new = lambda n, c: torch.empty((B, n, c), dtype=torch.float32, device=points.device)
@@ -305,12 +368,12 @@ class SA_SKN_Res_encoder(nn.Module):
         y = self.conv8.rows(X2, relu=True)
         EF_encoder._upsample(3, y, pt1, pt2, X1[..., :c2], trace)
         y = self.conv9.rows(X1, relu=True)
-        return self.conv_out.rows(y)
+        return self.conv_out.rows(y, out=out)
 
-    @torch.no_grad()
     def forward(self, features):
         """features (B,input_size,N) -> (B,output_size,N), the reference's layout."""
-        return self.forward_rows(features.transpose(1, 2).contiguous().float()).transpose(1, 2).contiguous()
+        with torch.set_grad_enabled(_builds_graph(self, None)):
+            return self.forward_rows(features.transpose(1, 2).contiguous().float()).transpose(1, 2).contiguous()
 
 
 class Folding(nn.Module):

@@ -790,6 +790,59 @@ def sa_attn_backward(P, idx, Ww1, Ww2, bw2, G, gP=None):
     return res
 
 
+def _edge_pool_lists(who, p_idx, pn_idx, B):
+    _lib.require_gpu(p_idx, pn_idx); _want(p_idx, _I32, f"{who}: p_idx"); _want(pn_idx, _I32, f"{who}: pn_idx")
+    if p_idx.dim() != 2 or p_idx.shape[0] != B or pn_idx.dim() != 3 or tuple(pn_idx.shape[:2]) != tuple(p_idx.shape):
+        raise _lib.HouvHipError(f"{who}: expected p_idx[{B},S] and pn_idx[{B},S,pk], got {tuple(p_idx.shape)} and {tuple(pn_idx.shape)}")
+    return p_idx.shape[1], pn_idx.shape[2]
+
+
+def edge_pool(feat, p_idx, pn_idx, out=None, want_arg=False):
+    """edge_preserve_sampling's feature half in one kernel (houv_edge_pool): feat[B,N,C] rows, p_idx[B,S]
+    and pn_idx[B,S,pk] int32 -> out[B,S,2C] = cat(feat[p_idx], max over the pk listed rows).  feat and `out` may be column slices
+    of wider row-major buffers; out's other columns are left alone.  want_arg: (out, arg[B,S,C] int8), the lowest slot that
+    attains each maximum (-1 for a column that is NaN in every listed row)."""
+    _lib.require_gpu_any(feat, out)
+    B, N, C, ldx = _rows(feat, "edge_pool: feat")
+    S, pk = _edge_pool_lists("edge_pool", p_idx, pn_idx, B)
+    if out is None:
+        out = torch.empty((B, S, 2 * C), dtype=_F32, device=feat.device)
+    if tuple(out.shape) != (B, S, 2 * C):
+        raise _lib.HouvHipError(f"edge_pool: out must be [{B},{S},{2 * C}], got {tuple(out.shape)}")
+    ldo = _rows(out, "edge_pool: out")[3]
+    arg = torch.empty((B, S, C), dtype=torch.int8, device=feat.device) if want_arg else None
+    with torch.cuda.device(feat.device):
+        ok = _lib.load().houv_edge_pool(ctypes_ptr(feat), ldx, _lib.ptr(p_idx), _lib.ptr(pn_idx), B, N, S, C, pk, ctypes_ptr(out), ldo,
+                                        _lib.ptr(arg), _lib.stream_of(feat))
+    _lib.check(ok, "houv_edge_pool")
+    return (out, arg) if want_arg else out
+
+
+def edge_pool_backward(g, p_idx, pn_idx, arg, N):
+    """The backward pass of edge_pool (houv_edge_pool_backward): g[B,S,2C] (the gradient of out; rows of
+    any stride), edge_pool's lists and arg, and the number of rows N of feat -> gfeat[B,N,C], every element written: the sum of
+    what landed on a row in ascending (s, slot), the centre first.  Deterministic: no float atomics.  The workspace (int32 only)
+    is allocated here."""
+    _lib.require_gpu_any(g)
+    B, S, C2, ldg = _rows(g, "edge_pool_backward: g")
+    S_, pk = _edge_pool_lists("edge_pool_backward", p_idx, pn_idx, B)
+    C = C2 // 2
+    _lib.require_gpu(arg)
+    if S_ != S or C2 != 2 * C or arg.dtype != torch.int8 or tuple(arg.shape) != (B, S, C):
+        raise _lib.HouvHipError(f"edge_pool_backward: expected g[{B},{S_},2C] and int8 arg[{B},{S_},C], got {tuple(g.shape)} and "
+                                f"{arg.dtype} {tuple(arg.shape)}")
+    dev = g.device
+    gfeat = torch.empty((B, int(N), C), dtype=_F32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.houv_edge_pool_backward_workspace_bytes(B, int(N), S, pk)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=dev)
+    with torch.cuda.device(dev):
+        ok = lib.houv_edge_pool_backward(ctypes_ptr(g), ldg, _lib.ptr(p_idx), _lib.ptr(pn_idx), _lib.ptr(arg), B, int(N), S, C, pk,
+                                         _lib.ptr(gfeat), C, _lib.ptr(ws), nbytes, _lib.stream_of(g))
+    _lib.check(ok, "houv_edge_pool_backward")
+    return gfeat
+
+
 # ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------

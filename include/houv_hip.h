@@ -626,6 +626,35 @@ int houv_sa_attn_backward(const float* P, int ldp, const int32_t* idx, int B, in
                           float* gWw1, float* gWw2, float* gbw2, void* workspace, long long workspace_bytes, void* stream);
 long long houv_sa_attn_backward_workspace_bytes(int B, int N, int C, int k);
 
+/* edge_preserve_sampling's feature half (model_utils.py:90-116) as one gather: feat[B,N,C] rows of stride
+ * ldx >= C, p_idx[B,S] the sampled rows, pn_idx[B,S,pk] each sample's neighbour list (an entry of either outside 0..N-1 is clamped
+ * into that range: nothing outside feat is read) ->
+ *   out[b,s,c]     = feat[b, p_idx[b,s], c]
+ *   out[b,s,C + c] = max over j of feat[b, pn_idx[b,s,j], c]          c in [0, C); out rows of stride ldo >= 2 C
+ * Columns 2 C .. ldo-1 of out are not touched, so `out` may point into a wider buffer.  The maximum keeps a running best that
+ * starts at slot 0 and is replaced only by a strictly greater element, so the stored value carries the bits of the winning slot's
+ * element and -0 against +0 keeps the earlier slot.  A NaN element is skipped; a column whose pk elements are all NaN is written
+ * as NaN.  arg_or_null, when given, is int8 [B,S,C] (dense): the LOWEST slot j that attains the maximum, -1 for an all-NaN column
+ * (houv_dense_conv_arg's rule).  The [B,S,pk,C] gather is never built; nothing is allocated; no atomics.  Rows are read and
+ * written four floats at a time when C, ldx and ldo are multiples of 4, feat and out aligned to 16 bytes and arg to 4; any other
+ * layout runs the same arithmetic one float at a time.  Served: 1 <= C <= 1024, 1 <= pk <= 32, S >= 1 with S (pk + 1) < 2^31,
+ * 1 <= N <= 16384, B >= 0 (B = 0 launches nothing); anything else, and a NULL pointer other than arg, is refused by name. */
+int houv_edge_pool(const float* feat, int ldx, const int32_t* p_idx, const int32_t* pn_idx, int B, int N, int S, int C, int pk,
+                   float* out, int ldo, int8_t* arg_or_null, void* stream);
+
+/* The backward pass of houv_edge_pool: g[B,S,2C] (rows of stride ldg >= 2 C), the forward's lists and arg ->  gfeat[B,N,C] (rows of
+ * stride ldgx >= C; columns beyond are not touched), every element written.  gfeat[b,n,c] is the fp32 sum of these terms, added
+ * one after the other starting from the first: s ascending; for each s first g[b,s,c] when clamp(p_idx[b,s]) == n, then, j
+ * ascending, g[b,s,C+c] when clamp(pn_idx[b,s,j]) == n and arg[b,s,c] == j; +0 where nothing lands.  No float atomics: two calls
+ * give the same bits, those of the sequential host loop.  The workspace holds int32 arrays only: the keys [B,S,pk+1] (slot 0 the
+ * centre), and their CSR inverse from houv_scatter_points_grad's stable counting sort, offsets [B,N+1] and order [B,S,pk+1].
+ * Served shapes, refusals and the vector / scalar layouts are houv_edge_pool's (g, gfeat, arg in place of feat, out, arg).
+ * workspace: houv_edge_pool_backward_workspace_bytes(B, N, S, pk) bytes (0 for arguments out of range), 16-byte aligned,
+ * caller-allocated; `workspace_bytes` is what the caller allocated, and a smaller, NULL or misaligned workspace is refused. */
+int houv_edge_pool_backward(const float* g, int ldg, const int32_t* p_idx, const int32_t* pn_idx, const int8_t* arg, int B, int N,
+                            int S, int C, int pk, float* gfeat, int ldgx, void* workspace, long long workspace_bytes, void* stream);
+long long houv_edge_pool_backward_workspace_bytes(int B, int N, int S, int pk);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
