@@ -92,7 +92,11 @@ _SIGNATURES = {
     "houv_edge_pool_backward": (ctypes.c_int, [_c_f, _int, _c_f, _c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _int, _c_f,
                                                ctypes.c_longlong, _c_f]),
     "houv_edge_pool_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int, _int]),
-    "houv_pose_forward": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
+    "houv_ef_expand": (ctypes.c_int, [_c_f, _int, _c_f, _int, _int, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _int, _c_f, _c_f]),
+    "houv_ef_expand_backward": (ctypes.c_int, [_c_f, _int, _c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _int, _c_f, _c_f, _int, _c_f,
+                                               _int, _c_f, _c_f, _c_f, _c_f, ctypes.c_longlong, _c_f]),
+    "houv_ef_expand_backward_workspace_bytes": (ctypes.c_longlong, [_int] * 5),
+    "houv_pose_forward": (ctypes.c_int,[_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 
 _lib = None

@@ -316,22 +316,76 @@ class Conv1x1(nn.Module):
         return y.view(*x.shape[:-1], W.shape[0]) if out is None else out
 
 
+class _EFExpandFunction(torch.autograd.Function):
+    """EF_expansion past its per-point projections as one autograd node (houv_ef_expand / houv_ef_expand_backward; DESIGN.md
+    section 9.16): proj (B,N,2O+2Or) = [U | V | P | Q], idx (B,N,k) int32 (a constant: no gradient), W2a (O r, O) (a column
+    slice of conv2's weight: its gradient returns through the slice), W3 (O,O), b3 (O) -> (B, N r, O).  Saved: proj, idx, the
+    int8 arg of the maxima and the two matrices; nothing of extent (B,k,N,.) is kept."""
+
+    @staticmethod
+    def forward(ctx, proj, idx, W2a, W3, b3, r):
+        out, arg = ops.ef_expand(proj, idx, W2a, W3, b3, r, want_arg=True)
+        ctx.r = r
+        ctx.save_for_backward(proj, idx, arg, W2a, W3)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, gout, _garg):
+        proj, idx, arg, W2a, W3 = ctx.saved_tensors
+        g = ops.ef_expand_backward(proj, idx, arg, W2a, W3, gout.contiguous(), ctx.r)
+        return g["gproj"], None, g["gW2a"], g["gW3"], g["gb3"], None
+
+
 class EF_expansion(nn.Module):
     """model_utils.py:24-55: x (B,input_size,N) -> (B,output_size,N*step_ratio), composed from houv_knn_feat, row gathers and
     houv_gemm_f32 (not fused: ECG uses it only when num_points > num_coarse + num_input; VRCNet's two expansions, 256 -> 64 and
     64 -> 256, are the same code).  The reference's view / permute chain
-    is kept: the (B,k,N,output_size*step_ratio) activations of conv2 are REINTERPRETED as (B,k,N*step_ratio,output_size)."""
+    is kept: the (B,k,N,output_size*step_ratio) activations of conv2 are REINTERPRETED as (B,k,N*step_ratio,output_size).
+    trainable=True (output_size in 64, 128, 256, step_ratio and k <= 8): with grad mode on, forward_rows
+    builds a graph -- two per-point products and one _EFExpandFunction node -- whose output equals the composition's within fp32
+    spread, not bit for bit; rows may require a gradient.  With the flag off, or grad mode off, the composition runs, no graph."""
 
-    def __init__(self, input_size, output_size=64, step_ratio=2, k=4):
+    def __init__(self, input_size, output_size=64, step_ratio=2, k=4, trainable=False):
         super().__init__()
         self.step_ratio, self.k, self.input_size, self.output_size = step_ratio, k, input_size, output_size
+        self.trainable = bool(trainable)
         self.conv1 = Conv1x1(input_size * 2, output_size, 2)
         self.conv2 = Conv1x1(input_size * 2 + output_size, output_size * step_ratio, 2)
         self.conv3 = Conv1x1(output_size, output_size, 2)
 
-    @torch.no_grad()
     def forward_rows(self, rows, idx=None, trace=None, name="knn_exp"):
-        """rows (B,N,input_size) -> (B,N*step_ratio,output_size); `name`: the key under which a trace records the lists."""
+        """rows (B,N,input_size) -> (B,N*step_ratio,output_size); `name`: the key under which a trace records the lists.
+        trainable=True with grad mode on: the graph path (_forward_rows_graph); otherwise the composition below, no graph."""
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward_rows_graph(rows, idx, trace, name)
+        with torch.no_grad():
+            return self._forward_rows_composed(rows, idx, trace, name)
+
+    def _forward_rows_graph(self, rows, idx, trace, name):
+        """everything that depends on one point alone is a per-point product -- [U | V] = x W1^T (+ b1
+        on U) and [P | Q] = relu(x) W2[:, O:]^T (+ b2 on P), two _LinearRowsFunction calls over column slices of the conv
+        weights -- and the per-edge rest is one node (_EFExpandFunction).  The lists come from the detached rows: constants,
+        as in the reference."""
+        B, N, C = rows.shape
+        O, r = self.output_size, self.step_ratio
+        with torch.no_grad():
+            if idx is None:
+                idx = ops.knn_feat(rows.detach(), self.k)
+            if trace is not None:
+                trace[name], trace[name + "_x"] = idx, rows.detach().clone()
+        x = rows.reshape(B * N, C)
+        W1, W2 = self.conv1.matrix(), self.conv2.matrix()
+        zeros = rows.new_zeros(O)
+        # one product per activation: W1's halves stacked as [W1c; W1n] (2O rows of C columns), conv2's x-columns as [W2c; W2n]
+        UV = _LinearRowsFunction.apply(x, torch.cat((W1[:, :C], W1[:, C:]), 0), torch.cat((self.conv1.bias, zeros)), False)
+        PQ = _LinearRowsFunction.apply(torch.relu(x), torch.cat((W2[:, O:O + C], W2[:, O + C:]), 0),
+                                       torch.cat((self.conv2.bias, rows.new_zeros(O * r))), False)
+        proj = torch.cat((UV, PQ), 1).view(B, N, 2 * O + 2 * O * r)
+        out, _ = _EFExpandFunction.apply(proj, idx.int().contiguous(), W2[:, :O], self.conv3.matrix(), self.conv3.bias, r)
+        return out
+
+    def _forward_rows_composed(self, rows, idx=None, trace=None, name="knn_exp"):
         B, N, C = rows.shape
         if idx is None:
             idx = ops.knn_feat(rows, self.k)
@@ -347,6 +401,5 @@ class EF_expansion(nn.Module):
         e = self.conv3.rows(e.view(B, k, N * self.step_ratio, self.output_size))
         return e.amax(dim=1)
 
-    @torch.no_grad()
     def forward(self, x):
         return self.forward_rows(x.transpose(1, 2).contiguous().float()).transpose(1, 2).contiguous()

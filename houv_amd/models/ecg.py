@@ -17,8 +17,9 @@ Dense_conv is ONE autograd node (houv_dense_conv_arg forward, houv_dense_conv_ba
 the weights, never an edge tensor); linear layers go through _LinearRowsFunction, row gathers through the ordered scatter of
 houv_scatter_points_grad, every pool through torch.max (one winner), and the reference's concatenations are torch.cat of
 [B, N, <= 1800] rows.  The k-NN lists, the samples and the three-NN weights are constants, as in the reference.  With the
-default ``trainable=False`` nothing changes: the tuple is computed forward-only, without a graph.  EF_expansion (scale >= 2) has
-no backward: ``trainable=True`` refuses it at construction.
+default ``trainable=False`` nothing changes: the tuple is computed forward-only, without a graph.  EF_expansion (scale >= 2) is
+not wired into this decoder's graph: ``trainable=True`` refuses it at construction (the block's backward now exists --
+EF_expansion(trainable=True), DESIGN.md section 9.16, which VRCNet's decoder uses -- and ECG can adopt it).
 
 Discrete decisions.  The network takes ~4000 arg-min / arg-sort decisions per cloud (furthest-point samples, k-NN lists in
 coordinate and in feature space, three-NN lists), and the reference does not agree with itself on them across precisions

@@ -15,9 +15,10 @@ The module tree and parameter names equal the reference's, so its checkpoints lo
 repository ships no trained weights: tests use seeded ones).  SA_module, SK_SA_module and SKN_Res_unit take trainable=True
 (one _SAAttnFunction node per attention block over houv_sa_attn_backward), and so does
 SA_SKN_Res_encoder (section 9.15: each edge-preserve pooling one _EdgePoolFunction node over houv_edge_pool /
-houv_edge_pool_backward, which the inference path shares); the decoder and Model stay inference only: the "train" prefix
-doubles the batch, draws two latent samples and needs the KL / MMD terms (the reference's MMD branch also calls a method that
-does not exist); it raises NotImplementedError.
+houv_edge_pool_backward, which the inference path shares) and MSAP_SKN_decoder (section 9.16: both EF_expansions through
+_EFExpandFunction over houv_ef_expand / houv_ef_expand_backward, Folding as the same three-part sum with a graph); Model stays
+inference only: the "train" prefix doubles the batch, draws two latent samples and needs the KL / MMD terms (the reference's
+MMD branch also calls a method that does not exist); it raises NotImplementedError.
 
 Two things the reference does that are easy to miss and are kept: Linear_ResBlock's ReLU is in place, so its residual branch
 sees relu(feature) and the CALLER's tensor is rectified too -- the decoder receives relu(feat) + generator(z), not feat +
@@ -34,8 +35,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..mm3d_pn2 import furthest_point_sample, knn_cross
-from ..model_utils_completion import (Conv1x1, EF_expansion, _LinearFunction, _LinearRowsFunction, _take_rows, _weight_grad, calc_cd,
-                                       calc_emd, gen_grid_up)
+from ..model_utils_completion import (Conv1x1, EF_expansion, _LinearFunction, _LinearRowsFunction, _RowGather, _take_rows,
+                                       _weight_grad, calc_cd, calc_emd, gen_grid_up)
 from .ecg import EF_encoder, _conv, _lin
 from .pcn import PCN_encoder
 
@@ -379,10 +380,13 @@ class SA_SKN_Res_encoder(nn.Module):
 class Folding(nn.Module):
     """vrcnet.py:70-113 on rows: (point_feat (B,n,input_size), global_feat (B,G)) -> (B,n*step_ratio,output_size).  The
     [B, G + input_size + 2, n*step_ratio] input is never built: the pre-activation is the sum of conv.weight's global columns
-    (one vector per cloud), its point columns (one per coarse point) and its grid columns (one per grid cell)."""
+    (one vector per cloud), its point columns (one per coarse point) and its grid columns (one per grid cell).  trainable=True
+    with grad mode on: the same sum with a graph (the two products through _LinearFunction / _LinearRowsFunction over column
+    slices of conv.weight, the two grid columns a torch product as below), to both inputs and the convolution."""
 
-    def __init__(self, input_size, output_size, step_ratio, global_feature_size=1024, num_models=1):
+    def __init__(self, input_size, output_size, step_ratio, global_feature_size=1024, num_models=1, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.input_size, self.output_size, self.step_ratio, self.num_models = input_size, output_size, step_ratio, num_models
         self.global_feature_size = global_feature_size
         self.conv = Conv1x1(input_size + global_feature_size + 2, output_size, 1)
@@ -390,8 +394,18 @@ class Folding(nn.Module):
         # parameter and not in the state_dict, as in the reference, but it follows the module to its device
         self.register_buffer("grid", gen_grid_up(step_ratio, 0.2).transpose(0, 1).contiguous(), persistent=False)
 
-    @torch.no_grad()
     def forward_rows(self, point_feat, global_feat):
+        B, n, _ = point_feat.shape
+        W, G = self.conv.matrix(), self.global_feature_size
+        if self.trainable and torch.is_grad_enabled():
+            g = _LinearFunction.apply(global_feat, W[:, :G], self.conv.bias, False)
+            p = _LinearRowsFunction.apply(_flat(point_feat), W[:, G:G + self.input_size], None, False).view(B, n, 1, -1)
+            q = self.grid @ W[:, G + self.input_size:].t()
+            return torch.relu((p + g.view(B, 1, 1, -1)) + q.view(1, 1, self.step_ratio, -1)).view(B, n * self.step_ratio, -1)
+        with torch.no_grad():
+            return self._forward_rows(point_feat, global_feat)
+
+    def _forward_rows(self, point_feat, global_feat):
         B, n, _ = point_feat.shape
         W, G = self.conv.matrix(), self.global_feature_size
         g = ops.gemm(global_feat, W[:, :G], shift=self.conv.bias)                                        # (B,out)
@@ -417,11 +431,20 @@ class Linear_ResBlock(nn.Module):
 
 class MSAP_SKN_decoder(nn.Module):
     """vrcnet.py:365-507: (global_feat (B,1024), input points (B,num_input,3)) -> (coarse_raw, coarse_high, coarse, fine), rows
-    of points."""
+    of points.
+
+    trainable=True: with grad mode on, forward builds a graph -- fc1..3 through _LinearFunction, the
+    encoder's own trainable path (coarse_raw carries a gradient into sam_res1), both EF_expansions through _EFExpandFunction,
+    conv_cup1/2 and conv_f1/2 through _LinearRowsFunction, Folding's graph path, and both row selections through _RowGather.
+    The furthest-point sample runs on the detached coarse_high and the score branch under no_grad: its top-k yields indices
+    only, so conv_s1..3 get no gradient, exactly as in the reference.  global_feat may require a gradient; a point_input that
+    does is refused.  With grad mode off, or trainable=False, the inference path runs and builds no graph; the graph path's
+    output equals it within fp32 spread, not bit for bit (the expansions' per-point split rounds differently)."""
 
     def __init__(self, num_coarse_raw, num_fps, num_coarse, num_fine, layers=(2, 2, 2, 2), knn_list=(10, 20), pk=10,
-                 points_label=False, local_folding=False):
+                 points_label=False, local_folding=False, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.num_coarse_raw, self.num_fps, self.num_coarse, self.num_fine = num_coarse_raw, num_fps, num_coarse, num_fine
         self.points_label, self.local_folding = points_label, local_folding
         self.fc1 = nn.Linear(1024, 1024)
@@ -430,11 +453,11 @@ class MSAP_SKN_decoder(nn.Module):
         self.dense_feature_size, self.expand_feature_size = 256, 64
         self.input_size = 4 if points_label else 3
         self.encoder = SA_SKN_Res_encoder(input_size=self.input_size, k=knn_list, pk=pk, output_size=self.dense_feature_size,
-                                          layers=layers)
+                                          layers=layers, trainable=trainable)
         self.up_scale = int(np.ceil(num_fine / (num_coarse_raw + 2048)))
         if self.up_scale >= 2:
             self.expansion1 = EF_expansion(input_size=self.dense_feature_size, output_size=self.expand_feature_size,
-                                           step_ratio=self.up_scale, k=4)
+                                           step_ratio=self.up_scale, k=4, trainable=trainable)
             self.conv_cup1 = Conv1x1(self.expand_feature_size, self.expand_feature_size)
         else:
             self.expansion1 = None
@@ -445,15 +468,66 @@ class MSAP_SKN_decoder(nn.Module):
         self.conv_s3 = Conv1x1(8, 1)
         if local_folding:
             self.expansion2 = Folding(input_size=self.expand_feature_size, output_size=self.dense_feature_size,
-                                      step_ratio=num_fine // num_coarse)
+                                      step_ratio=num_fine // num_coarse, trainable=trainable)
         else:
             self.expansion2 = EF_expansion(input_size=self.expand_feature_size, output_size=self.dense_feature_size,
-                                           step_ratio=num_fine // num_coarse, k=4)
+                                           step_ratio=num_fine // num_coarse, k=4, trainable=trainable)
         self.conv_f1 = Conv1x1(self.dense_feature_size, self.expand_feature_size)
         self.conv_f2 = Conv1x1(self.expand_feature_size, 3)
 
-    @torch.no_grad()
     def forward(self, global_feat, point_input, trace=None):
+        if self.trainable and torch.is_grad_enabled():
+            if point_input.requires_grad:
+                raise ValueError("MSAP_SKN_decoder: the gradient with respect to the input cloud is not built (point_input.requires_grad)")
+            return self._forward_train(global_feat, point_input, trace)
+        with torch.no_grad():
+            return self._forward(global_feat, point_input, trace)
+
+    def _forward_train(self, global_feat, point_input, trace):
+        """forward with a graph: the same steps in the same order; every discrete decision from detached values."""
+        B = global_feat.shape[0]
+        lin = lambda fc, t, relu: _LinearFunction.apply(t, fc.weight, fc.bias, relu)
+        raw = lin(self.fc3, lin(self.fc2, lin(self.fc1, global_feat, True), True), False)
+        coarse_raw = raw.view(B, 3, self.num_coarse_raw).transpose(1, 2).contiguous()
+        points = torch.cat((coarse_raw, point_input), dim=1)
+        if self.points_label:
+            label = points.new_ones((B, points.shape[1], 1))
+            label[:, :self.num_coarse_raw] = 0
+            points = torch.cat((points, label), dim=2)
+        dense = self.encoder.forward_rows(points, trace)
+        if self.up_scale >= 2:
+            dense = self.expansion1.forward_rows(dense, trace=trace, name="knn_exp1")
+        feats = _conv(self.conv_cup1, dense, relu=True)
+        coarse_high = _conv(self.conv_cup2, feats)
+        coarse = coarse_high
+        if coarse.shape[1] > self.num_fps:
+            with torch.no_grad():
+                idx = furthest_point_sample(coarse_high.detach().contiguous(), self.num_fps)
+            if trace is not None:
+                trace["fps_out"] = idx
+            coarse, feats = _RowGather.apply(coarse_high, idx).contiguous(), _RowGather.apply(feats, idx).contiguous()
+        if coarse.shape[1] > self.num_coarse:
+            with torch.no_grad():                # the scores select rows and carry no gradient: top-k returns indices only
+                s = self.conv_s3.rows(self.conv_s2.rows(self.conv_s1.rows(feats.detach(), relu=True), relu=True))
+                idx = F.softplus(s).view(B, -1).topk(self.num_coarse, dim=1)[1].int()
+            if trace is not None:
+                trace["topk"] = idx
+            coarse, feats = _RowGather.apply(coarse, idx).contiguous(), _RowGather.apply(feats, idx).contiguous()
+        if coarse.shape[1] < self.num_fine:
+            step = self.num_fine // self.num_coarse
+            if self.local_folding:
+                up = self.expansion2.forward_rows(feats, global_feat)
+                centre = coarse.unsqueeze(2).expand(-1, -1, step, -1).reshape(B, self.num_fine, 3)
+                fine = _conv(self.conv_f2, _conv(self.conv_f1, up, relu=True)) + centre
+            else:
+                up = self.expansion2.forward_rows(feats, trace=trace, name="knn_exp2")
+                fine = _conv(self.conv_f2, _conv(self.conv_f1, up, relu=True))
+        else:
+            assert coarse.shape[1] == self.num_fine
+            fine = coarse
+        return coarse_raw, coarse_high, coarse, fine
+
+    def _forward(self, global_feat, point_input, trace=None):
         B = global_feat.shape[0]
         raw = _linear(self.fc3, _linear(self.fc2, _linear(self.fc1, global_feat, relu=True), relu=True))
         coarse_raw = raw.view(B, 3, self.num_coarse_raw).transpose(1, 2).contiguous()

@@ -843,6 +843,80 @@ def edge_pool_backward(g, p_idx, pn_idx, arg, N):
     return gfeat
 
 
+def _ef_expand_args(who, proj, idx, W2a, W3, r):
+    """(B, N, O, k, ldp, ldw) of ef_expand's operands: proj[B,N,2O+2Or] rows (one row stride), idx[B,N,k] int32, W2a[O r, O] rows
+    of any stride (a column slice of conv2's weight), W3[O,O] dense."""
+    _lib.require_gpu_any(proj, W2a, W3)
+    B, N, W, ldp = _rows(proj, f"{who}: proj")
+    r = int(r)
+    O = W3.shape[0]
+    if W3.dim() != 2 or W3.shape[1] != O or not W3.is_contiguous() or r < 1 or W != 2 * O + 2 * O * r:
+        raise _lib.HouvHipError(f"{who}: expected dense W3[O,O] and proj[B,N,2O+2Or], got W3 {tuple(W3.shape)}, proj {tuple(proj.shape)}, r={r}")
+    if W2a.dim() != 2 or tuple(W2a.shape) != (O * r, O) or W2a.stride(1) != 1 or W2a.stride(0) < O:
+        raise _lib.HouvHipError(f"{who}: expected W2a[{O * r},{O}] rows with unit column stride, got {tuple(W2a.shape)} strides {tuple(W2a.stride())}")
+    _lib.require_gpu(idx); _want(idx, _I32, f"{who}: idx")
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
+        raise _lib.HouvHipError(f"{who}: expected idx[{B},{N},k], got {tuple(idx.shape)}")
+    return B, N, O, idx.shape[2], ldp, W2a.stride(0)
+
+
+def ef_expand(proj, idx, W2a, W3, b3, r, out=None, want_arg=False):
+    """EF_expansion past its per-point projections in one kernel (houv_ef_expand): proj[B,N,2O+2Or] =
+    [U | V | P | Q] rows, idx[B,N,k] int32, W2a[O r, O] (the first O columns of conv2's weight; a column slice is fine), W3[O,O],
+    b3[O] -> out[B, N r, O], the maximum over the k listed neighbours of conv3(relu(conv2(...))).  proj and `out` may be column
+    slices of wider row-major buffers.  want_arg: (out, arg[B, N r, O] int8), the lowest slot that attains each maximum (-1 for
+    a column that is NaN at every slot)."""
+    B, N, O, k, ldp, ldw = _ef_expand_args("ef_expand", proj, idx, W2a, W3, r)
+    r = int(r)
+    _lib.require_gpu(b3); _want(b3, _F32, "ef_expand: b3")
+    if tuple(b3.shape) != (O,):
+        raise _lib.HouvHipError(f"ef_expand: b3 must be [{O}], got {tuple(b3.shape)}")
+    if out is None:
+        out = torch.empty((B, N * r, O), dtype=_F32, device=proj.device)
+    _lib.require_gpu_any(out)
+    if tuple(out.shape) != (B, N * r, O):
+        raise _lib.HouvHipError(f"ef_expand: out must be [{B},{N * r},{O}], got {tuple(out.shape)}")
+    ldo = _rows(out, "ef_expand: out")[3]
+    arg = torch.empty((B, N * r, O), dtype=torch.int8, device=proj.device) if want_arg else None
+    with torch.cuda.device(proj.device):
+        ok = _lib.load().houv_ef_expand(ctypes_ptr(proj), ldp, _lib.ptr(idx), B, N, O, k, r, ctypes_ptr(W2a), ldw, ctypes_ptr(W3),
+                                        _lib.ptr(b3), ctypes_ptr(out), ldo, _lib.ptr(arg), _lib.stream_of(proj))
+    _lib.check(ok, "houv_ef_expand")
+    return (out, arg) if want_arg else out
+
+
+def ef_expand_backward(proj, idx, arg, W2a, W3, g, r, gproj=None):
+    """The backward pass of ef_expand (houv_ef_expand_backward): ef_expand's operands, its arg and
+    g[B, N r, O] (rows of any stride) -> {"gproj": [B,N,2O+2Or] (every element written; `gproj`, when given, may be a column
+    slice), "gW2a": [O r, O], "gW3": [O,O], "gb3": [O]}.  Deterministic: no float atomics.  The workspace is allocated here."""
+    B, N, O, k, ldp, ldw = _ef_expand_args("ef_expand_backward", proj, idx, W2a, W3, r)
+    r = int(r)
+    _lib.require_gpu_any(g); _lib.require_gpu(arg)
+    if tuple(g.shape) != (B, N * r, O) or arg.dtype != torch.int8 or tuple(arg.shape) != (B, N * r, O):
+        raise _lib.HouvHipError(f"ef_expand_backward: expected g[{B},{N * r},{O}] and int8 arg of that shape, got {tuple(g.shape)} and "
+                                f"{arg.dtype} {tuple(arg.shape)}")
+    ldg = _rows(g, "ef_expand_backward: g")[3]
+    dev = proj.device
+    W = 2 * O + 2 * O * r
+    if gproj is None:
+        gproj = torch.empty((B, N, W), dtype=_F32, device=dev)
+    _lib.require_gpu_any(gproj)
+    if tuple(gproj.shape) != (B, N, W):
+        raise _lib.HouvHipError(f"ef_expand_backward: gproj must be [{B},{N},{W}], got {tuple(gproj.shape)}")
+    ldgp = _rows(gproj, "ef_expand_backward: gproj")[3]
+    res = {"gproj": gproj, "gW2a": torch.empty((O * r, O), dtype=_F32, device=dev), "gW3": torch.empty((O, O), dtype=_F32, device=dev),
+           "gb3": torch.empty((O,), dtype=_F32, device=dev)}
+    lib = _lib.load()
+    nbytes = lib.houv_ef_expand_backward_workspace_bytes(B, N, O, k, r)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=dev)
+    with torch.cuda.device(dev):
+        ok = lib.houv_ef_expand_backward(ctypes_ptr(proj), ldp, _lib.ptr(idx), _lib.ptr(arg), B, N, O, k, r, ctypes_ptr(W2a), ldw,
+                                         ctypes_ptr(W3), ctypes_ptr(g), ldg, ctypes_ptr(gproj), ldgp, _lib.ptr(res["gW2a"]),
+                                         _lib.ptr(res["gW3"]), _lib.ptr(res["gb3"]), _lib.ptr(ws), nbytes, _lib.stream_of(proj))
+    _lib.check(ok, "houv_ef_expand_backward")
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------
 # torch.ops.houv.* registration (PyTorch-ROCm custom ops; the schema marks the in-place outputs)
 # ---------------------------------------------------------------------------------------------------

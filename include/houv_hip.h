@@ -655,6 +655,36 @@ int houv_edge_pool_backward(const float* g, int ldg, const int32_t* p_idx, const
                             int S, int C, int pk, float* gfeat, int ldgx, void* workspace, long long workspace_bytes, void* stream);
 long long houv_edge_pool_backward_workspace_bytes(int B, int N, int S, int pk);
 
+/* EF_expansion (completion/model_utils.py:24-55) past its per-point projections.  proj[B*N, 2 O + 2 O r]
+ * = [U | V | P | Q] (rows of stride ldp), idx[B,N,k] (an entry outside 0..N-1 is clamped into that range), W2a[O r, O] (rows of
+ * stride ldw: the first O columns of conv2's weight), W3[O,O] and b3[O] (dense).  With m = idx[b,n,j], per sub-row s < r:
+ *   h1 = U_n + V_m;   t = W2a[s O : (s+1) O, :] relu(h1) + P_n[s O : (s+1) O] + Q_m[s O : (s+1) O];   e_j = W3 relu(t) + b3
+ *   out[b, n r + s, c] = max over j of e_j[c]                           out rows of stride ldo >= O, other columns not touched
+ * relu keeps a NaN.  The maximum is houv_edge_pool's: a running best from slot 0 replaced only by a strictly greater value, a NaN
+ * skipped, an all-NaN column written as NaN; arg_or_null, when given, is int8 [B, N r, O] (dense), the LOWEST slot that attains
+ * the maximum, -1 for an all-NaN column.  Both products run on the fp32-input MFMA.  Nothing is allocated; no atomics.  Served:
+ * O in {64, 128, 256}, 1 <= r <= 8, 1 <= k <= 8, 1 <= N <= 16384 with N r O < 2^31, B >= 0 (B = 0 launches nothing); anything
+ * else, and a NULL pointer other than arg, is refused by name. */
+int houv_ef_expand(const float* proj, int ldp, const int32_t* idx, int B, int N, int O, int k, int r, const float* W2a, int ldw,
+                   const float* W3, const float* b3, float* out, int ldo, int8_t* arg_or_null, void* stream);
+
+/* The backward pass of houv_ef_expand: its inputs, the forward's arg and g[B, N r, O] (rows of stride ldg) -> gproj[B*N, 2 O + 2 O r]
+ * (rows of stride ldgp, every element of those columns written), gW2a[O r, O], gW3[O, O], gb3[O] (dense).  The forward is
+ * recomputed from proj; with ge_j[s][c] = g[b, n r + s, c] where arg == j and +0 elsewhere:
+ *   gh2 = W3^T ge (per s);  gt = gh2 [t > 0];  gh1 = (sum over s of W2a_s^T gt_s) [h1 > 0]
+ *   gU_n = sum_j gh1;  gP_n = sum_j gt;  gV_m, gQ_m = the same terms over the edges that list m, in ascending (n, j)
+ *   gW3 = sum ge (x) relu(t);  gW2a = sum gt (x) relu(h1);  gb3 = sum ge
+ * The clouds are taken in groups of whole clouds (about 32768 edges each), one after the other, so the workspace does not grow
+ * with B.  A group's per-edge terms go to the workspace; the list sums follow houv_scatter_points_grad's CSR inverse, the weight
+ * sums are houv_gemm_f32 products over fixed row chunks whose partials are added to the running sum in chunk order, groups
+ * ascending, gb3 per-chunk partials likewise.  No float atomics: two calls give the same bits.  Served shapes and refusals are
+ * houv_ef_expand's; B = 0 writes zero weight gradients.  workspace: houv_ef_expand_backward_workspace_bytes(B, N, O, k, r) bytes (0 for arguments out of
+ * range), 16-byte aligned, caller-allocated; a smaller, NULL or misaligned workspace is refused. */
+int houv_ef_expand_backward(const float* proj, int ldp, const int32_t* idx, const int8_t* arg, int B, int N, int O, int k, int r,
+                            const float* W2a, int ldw, const float* W3, const float* g, int ldg, float* gproj, int ldgp,
+                            float* gW2a, float* gW3, float* gb3, void* workspace, long long workspace_bytes, void* stream);
+long long houv_ef_expand_backward_workspace_bytes(int B, int N, int O, int k, int r);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
