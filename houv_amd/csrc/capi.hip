@@ -64,7 +64,8 @@ extern "C" int houv_debug_set(const char* name, long long value) {
   // accepted values: lo..hi in steps of `step` (gemm_split: 0, 3 or 6 part products -- any other count is not a kernel)
   const struct { const char* name; std::atomic<int>* knob; long long lo, hi, step; } ints[] = {
       {"solve_predict", &g_debug.pred_mode, 0, 2, 1}, {"knn_split", &g_debug.knn_split, 0, 1, 1},
-      {"attn_split", &g_debug.attn_split, 0, 1, 1},   {"gemm_split", &g_debug.gemm_split, 0, 6, 3}};
+      {"attn_split", &g_debug.attn_split, 0, 1, 1},   {"gemm_split", &g_debug.gemm_split, 0, 6, 3},
+      {"solve_max_workgroups", &g_debug.max_workgroups, 0, 0x7fffffff, 1}};
   if (name && !strcmp(name, "solve_stats")) {
     g_debug.stats = (unsigned long long)value;
     return 1;
@@ -75,6 +76,10 @@ extern "C" int houv_debug_set(const char* name, long long value) {
   }
   if (name && !strcmp(name, "solve_cull_stats")) {
     g_debug.cull_stats = (unsigned long long)value;
+    return 1;
+  }
+  if (name && !strcmp(name, "solve_sched")) {
+    g_debug.sched = (unsigned long long)value;
     return 1;
   }
   for (const auto& k : ints)

@@ -39,6 +39,8 @@ inline bool check_launch(const char* what) {
 //   "solve_stats"     device address of 8 uint64 counters the fused loop adds to (0 = off): see SolveArgs::stats
 //   "solve_walk_hist" device address of 16 uint64 counters (0 = off): the term masks the pruned walks see, see SolveArgs::walk_hist
 //   "solve_cull_stats" device address of 4 uint64 counters (0 = off): the group cull of the box tests, see SolveArgs::cull_stats
+//   "solve_sched"     device address of 8 x 4 uint64 counters (0 = off): per XCD, what its workgroups ran and when, see SolveArgs::sched
+//   "solve_max_workgroups"  houv_solve_stage: cap of the persistent grid (0 = off); a test aid, like ws_valid < 0
 //   "knn_split"       houv_knn: 1 references split over the four waves of a workgroup (same lists), 0 the single-scan kernel
 //   "attn_split"      houv_attention_f32: 1 bf16 matrix pipe with three-part splits (full tiles), 0 fp32-input MFMA kernel
 //   "gemm_split"      houv_gemm_f32: 0 fp32-input MFMA, 6 / 3 = bf16 part products per fp32 product (gemm.hip, gemm_split_kernel)
@@ -47,6 +49,8 @@ struct DebugKnobs {
   std::atomic<unsigned long long> stats{0ull};
   std::atomic<unsigned long long> walk_hist{0ull};
   std::atomic<unsigned long long> cull_stats{0ull};
+  std::atomic<unsigned long long> sched{0ull};
+  std::atomic<int> max_workgroups{0};
   std::atomic<int> knn_split{1};         // houv_knn (N >= 512, k = 16 / 20): four waves per 64 queries, a quarter of the references each; 0: one wave per 64 queries
   std::atomic<int> attn_split{1};        // houv_attention_f32 on the bf16 matrix pipe (attention.hip, attention_split_kernel); 0: fp32-input MFMA
   std::atomic<int> gemm_split{6};        // houv_gemm_f32 on the bf16 matrix pipe: 6 / 3 part products per fp32 product (0: fp32-input MFMA)

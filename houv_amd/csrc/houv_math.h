@@ -594,4 +594,19 @@ HOUV_HD inline void kabsch_rotation(const T H[9], T R[9]) {
   }
 }
 
+// ---- stage scheduling (houv_solve_stage, solve.hip): a stage of n_iters iterations is cut into chunks of chunk_iters (the last
+// one what is left); ticket t of the persistent grid is the item (chunk = t / ninst, hypothesis = t % ninst), chunk-major ----
+HOUV_HD inline int sched_chunks(int n_iters, int chunk_iters) { return (n_iters - 1) / chunk_iters + 1; }   // n_iters, chunk_iters >= 1; no overflow
+// items of a stage; 64-bit on the host (the entry point refuses a stage whose tickets do not fit an int), int in the kernel
+HOUV_HD inline long long sched_items64(int ninst, int n_iters, int chunk_iters) {
+  return (long long)ninst * sched_chunks(n_iters, chunk_iters);
+}
+HOUV_HD inline int sched_items(int ninst, int n_iters, int chunk_iters) { return ninst * sched_chunks(n_iters, chunk_iters); }
+// iterations of chunk `chunk`; it starts at steps_done + chunk * chunk_iters and finds the workspace valid when the stage did
+// or when chunk > 0
+HOUV_HD inline int sched_item_iters(int n_iters, int chunk_iters, int chunk) {
+  const int left = n_iters - chunk * chunk_iters;
+  return left < chunk_iters ? left : chunk_iters;
+}
+
 }  // namespace houv

@@ -4,6 +4,8 @@
 //   pose from 8 scalars -> move the source cloud -> 4-metric bidirectional Chamfer (two LDS-resident
 //   brute-force sweeps) -> top-k robust loss -> closed-form gradient -> Adam step, `n_iters` times,
 // with both clouds resident in LDS and NOTHING but the 24-double state touching HBM in between.
+// houv_solve_iterate[_pruned] launch one workgroup per hypothesis; houv_solve_stage[_pruned] launch a persistent grid that draws
+// (hypothesis, chunk) tickets, each such item being exactly that launch's work for one hypothesis (Stage scheduling).
 // It replaces the PyTorch loop of predict_model (registration/models/houv.py:106-138; loss :209-222,
 // model_utils_completion.py:83-100,157-166) and of getPredict_angle (registration/train_utils.py:359-456),
 // which per iteration launches 8 NmDistanceKernel + 8 NmDistanceGradKernel + 8 topk + ~150 small kernels
@@ -52,6 +54,15 @@ struct SolveArgs : SolveCommon {
   unsigned long long* cull_stats;  // houv_debug_set("solve_cull_stats", device pointer): 4 counters of the box tests' group cull
                                    // (prune_masks): groups tested, boxes surviving, per-query tests executed, per-query tests of a
                                    // loop over all boxes; read where it is used only (fresh)
+  // Stage scheduling (houv_solve_stage[_pruned]).  sched_ws == nullptr: one workgroup per hypothesis, n_iters
+  // iterations (houv_solve_iterate[_pruned]).  Otherwise a persistent grid draws tickets from sched_ws[0]: ticket t is the item
+  // (chunk = t / ninst, hypothesis = t % ninst), chunk_iters iterations of the stage's n_iters (the last chunk what is left).
+  int* sched_ws;     // int32 [4 + P*K]: [0] ticket counter, [1] status (non-zero: a poll ran out of time), [2..3] spare,
+                     // [4 + h] = done[h], chunks of hypothesis h that are finished AND published; zeroed by the call
+  int chunk_iters;
+  unsigned long long* sched;   // houv_debug_set("solve_sched", device pointer): per XCD (HW_REG_XCC_ID, 0..7) 4 counters: items run
+                               // by its workgroups, sum of the workgroups' durations, earliest start, latest end (100-MHz ticks
+                               // of s_memrealtime; the caller presets the minima to all ones); read where it is used only (fresh)
 };
 
 constexpr int kRescanBatch = 4;       // references per batch of a rescan's LDS reads (recover_nn)
@@ -65,6 +76,18 @@ constexpr int kRefresh = 4;
 // (profiles/r11_ab_term_anchors.txt): no limit 0.3510 / 0.3520, 12 -> 0.3520 / 0.3526, 6 -> 0.3544 / 0.3550 us per
 // hypothesis-iteration, identical results.
 constexpr int kTermMaxAge = 0;
+// stage scheduling: 100-MHz ticks (s_memrealtime) a poll of done[h] allows per iteration of the stage: 20 ms, derived where it is used
+constexpr unsigned long long kPollTicksPerIter = 2000000ull;
+
+// words of an item's scalars in LDS (solve_kernel's `iw`)
+constexpr int kItemSteps = 0, kItemIters = 1, kItemWsValid = 2, kItemInst = 3, kItemClk = 4;   // [kItemClk .. +3]: the stats' two stamps
+
+// the XCD (0..7) this wave runs on
+__device__ __forceinline__ int xcc_id() {
+  int v;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+  return v & 7;
+}
 
 struct Smem {
   float4* tgt;     // [Mpad]
@@ -414,19 +437,96 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   constexpr int TS = (PRUNE == 3) ? 1 : 0;                      // visit masks over super-tiles of 32 << TS references
   constexpr int kPad = kSub << TS;
   extern __shared__ __attribute__((aligned(512))) unsigned char smem_raw[];   // 512 B: the pruned walk's XOR-rotated gathers
+  // Scheduling diagnostic: this workgroup's start stamp and item count wait in free ctl words (not in registers)
+  if (fresh(a.sched) && tid_x() == 0) {
+    int* ctl = carve(smem_raw, a.N, a.M, BLOCK, PRUNE ? BLOCK * Q : 0, kPad).ctl;
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    ctl[2] = (int)(unsigned)t0;
+    ctl[3] = (int)(unsigned)(t0 >> 32);
+    ctl[4] = 0;
+  }
+  // The ticket loop of a stage (a.sched_ws set; one pass and no tickets otherwise).  Everything below it is one ITEM: what a
+  // launch of houv_solve_iterate[_pruned] does for one hypothesis, with the item's own steps_done / n_iters / ws_valid.
+#pragma unroll 1
+  for (;;) {
+  // The thread index is taken anew per item (and per use inside the iteration loop): what the prologue derives from it per lane
+  // is computed in the item -- not once in front of the ticket loop, where it would stay in VGPRs through every iteration loop.
+  // For the same reason the prologue's uniform values that the vector unit forms (the poll limit, the pose, Adam's scalars, the
+  // padding vector) start from fresh() arguments.
   const int N = a.N, M = a.M;
   const Smem sm = carve(smem_raw, N, M, BLOCK, PRUNE ? BLOCK * Q : 0, kPad);
   const int tid = tid_x();
   const int ninst = a.P * a.K;
-  // XCD-aware placement: workgroups b and b+8 share an XCD (and its L2), so give each XCD a contiguous
-  // range of hypotheses -> the K restarts of one pair read the pair's clouds through ONE L2.
-  int inst = blockIdx.x;
-  if ((ninst & 7) == 0) inst = (blockIdx.x & 7) * (ninst >> 3) + (blockIdx.x >> 3);
+  int inst = blockIdx.x, steps_done = a.steps_done, n_iters = a.n_iters, ws_valid = a.ws_valid, chunk = 0;
+  if (a.sched_ws) {
+    // Tickets are drawn in order by resident workgroups, chunk-major: the earlier chunk of this hypothesis was drawn ninst
+    // tickets before, so it is finished or running -- the wait below checks, it does not schedule, and cannot deadlock at any
+    // grid size (the chain ends at chunk 0).
+    if (tid == 0) {
+      int t = atomicAdd(a.sched_ws, 1);
+      const int c = t / ninst;
+      if (t < sched_items(ninst, a.n_iters, a.chunk_iters) && c > 0) {
+        // Consumer side of the hand-off (one lane polls relaxed, then ONE agent acquire; its wait holds the barrier below
+        // until this CU's L1 is invalidated; plain loads follow).  The poll is bounded in TIME: the chain a wait depends on is
+        // the earlier chunks of this one hypothesis, one after the other, i.e. fewer than n_iters iterations; the longest
+        // iteration of a supported shape is the 4096-point brute-force kernel's, 2 x 4096^2 point pairs on one CU = 1.6 ms
+        // (4 x the 0.78 ms a workgroup-iteration of profiles/r03_pmc_summary.txt's 2048-point brute-force launch takes, at one
+        // workgroup per CU instead of two).  kPollTicksPerIter allows 20 ms per iteration: 12 x that, for a slow clock and for
+        // other streams' kernels sharing the CU.
+        const int* done = a.sched_ws + 4 + (t - c * ninst);
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        const unsigned long long limit = (unsigned long long)fresh(a.n_iters) * kPollTicksPerIter;   // (formed here, not hoisted)
+        while (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c) {
+          if (__builtin_amdgcn_s_memrealtime() - t0 > limit) {
+            __hip_atomic_store(a.sched_ws + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            t = 0x7fffffff;   // every thread leaves the ticket loop
+            break;
+          }
+          __builtin_amdgcn_s_sleep(32);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      sm.ctl[1] = t;
+    }
+    __syncthreads();   // the ticket, and behind an acquire: the earlier chunk's state (must be fresh: plain loads behind this
+                       // acquire, the guide's "plain stores + agent release / agent acquire + plain loads" form) and its NN
+                       // records in nn_ws rows 0..7 (may be stale: any in-range remembered index is an attained bound, so a stale
+                       // record costs visits, not correctness; rows 8..15 are scratch within an iteration)
+    const int t = __builtin_amdgcn_readfirstlane(sm.ctl[1]);
+    if (t >= sched_items(ninst, a.n_iters, a.chunk_iters)) break;
+    chunk = t / ninst;
+    inst = t - chunk * ninst;
+    steps_done = a.steps_done + chunk * a.chunk_iters;
+    n_iters = sched_item_iters(a.n_iters, a.chunk_iters, chunk);
+    ws_valid = (a.ws_valid != 0 || chunk > 0) ? 1 : 0;
+    if (fresh(a.sched) && tid == 0) sm.ctl[4] += 1;
+  } else {
+    // XCD-aware placement: workgroups b and b+8 share an XCD (and its L2), so give each XCD a contiguous
+    // range of hypotheses -> the K restarts of one pair read the pair's clouds through ONE L2.
+    if ((ninst & 7) == 0) inst = (blockIdx.x & 7) * (ninst >> 3) + (blockIdx.x >> 3);
+    if (fresh(a.sched) && tid == 0) sm.ctl[4] = 1;
+  }
+  // The item's scalars wait in LDS, not in SGPRs, through the iteration loop (item(i) where a uniform value is needed, iw[i] in
+  // the one-thread tails): the 64 bytes smem_bytes adds for alignment leave at least 52 behind the last array.
+  int* const iw = PRUNE ? reinterpret_cast<int*>(sm.anchor + kAnchorFloats) : sm.ctl + 8 + BLOCK / 64;
+  if (tid == 0) {
+    iw[kItemSteps] = steps_done;
+    iw[kItemIters] = n_iters;
+    iw[kItemWsValid] = ws_valid;
+    iw[kItemInst] = inst;
+  }
+  auto item = [&](int i) {
+    return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(fresh_lds(reinterpret_cast<const float*>(iw + i))));
+  };
   const int pair = inst / a.K;
   const buf_t src = make_buf(a.src + (size_t)pair * N * 3, N * 12);
   const float* __restrict__ tgt = a.tgt + (size_t)pair * M * 3;
   const int npad = (N + kPad - 1) / kPad * kPad, mpad = (M + kPad - 1) / kPad * kPad;
-  const float4 pad4 = make_float4(INFINITY, INFINITY, INFINITY, 0.f);   // padding references never win
+  // padding references never win; the +inf is opaque so that this vector is the prologue's own (as the same constant as the
+  // walk's it was kept in four VGPRs from the head of the ticket loop on, and spilled)
+  const float inf = __uint_as_float(fresh(0x7f800000u));
+  const float4 pad4 = make_float4(inf, inf, inf, 0.f);
 
   for (int j = tid; j < mpad; j += BLOCK) sm.tgt[j] = (j < M) ? make_float4(tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2], 0.f) : pad4;
   for (int j = N + tid; j < npad; j += BLOCK) sm.mov[j] = pad4;
@@ -462,12 +562,12 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
 #pragma unroll
     for (int k = 0; k < 8; ++k) p[k] = (float)sm.state[k];
     Pose f;
-    pose_forward(p, a.angle_base, a.trans_mode, f);
+    pose_forward(p, fresh(a.angle_base), fresh(a.trans_mode), f);
     store_pose(sm.pose, f);
   }
   if (tid == kAdamTid) {
-    const int step = a.steps_done + 1;
-    const AdamScalars asc = adam_scalars(step, a.lr, a.beta1, a.beta2);
+    const int step = steps_done + 1;
+    const AdamScalars asc = adam_scalars(step, fresh(a.lr), fresh(a.beta1), fresh(a.beta2));
     sm.adam[(step & 1) * 2 + 0] = asc.step_size;
     sm.adam[(step & 1) * 2 + 1] = asc.bc2_sqrt;
   }
@@ -482,9 +582,8 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       const float v = __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x));
       r2 = (v <= r2) ? r2 : ((v < INFINITY) ? v : INFINITY);
     }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) r2 = fmaxf(r2, __shfl_xor(r2, o, 64));
-    if ((tid & 63) == 0) sm.red[tid >> 6] = r2;
+    r2 = wave_fmax_to_lane63(r2);   // r2 is never NaN; a maximum does not depend on the order it is taken in
+    if ((tid & 63) == 63) sm.red[tid >> 6] = r2;
     if (tid == 0) {
       sm.ctl[0] = (int)(((1u << NMET) - 1u) * 0x11u);
       reinterpret_cast<unsigned*>(sm.anchor)[kTermAges] = 0u;
@@ -499,10 +598,12 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     }
   }
 
-  unsigned long long clk0 = 0ull, rt0 = 0ull;   // two stamps per LAUNCH (not per iteration), only when the counters are on
-  if (a.stats) {
-    clk0 = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
+  if (a.stats && tid == 0) {   // two stamps per ITEM (not per iteration), only when the counters are on
+    const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
+    iw[kItemClk] = (int)(unsigned)clk0;
+    iw[kItemClk + 1] = (int)(unsigned)(clk0 >> 32);
+    iw[kItemClk + 2] = (int)(unsigned)rt0;
+    iw[kItemClk + 3] = (int)(unsigned)(rt0 >> 32);
   }
   constexpr int NW = BLOCK / 64;
   constexpr unsigned kAllMet = (1u << NMET) - 1u;
@@ -517,9 +618,9 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
   // once, the two addresses lived in VGPRs through every walk of the loop)
   auto red_row = [&](int dir) { return sm.red + ((size_t)dir * NW + (tid_x() >> 6)) * kRedStride; };
 #pragma unroll 1
-  for (int it = 0; it < a.n_iters; ++it) {
+  for (int it = 0; it < item(kItemIters); ++it) {
     if (a.pred_mode == 1) pred_a = 0u;
-    const bool allgrad = a.pred_mode == 2 || ((PRUNE != 0) && (((a.steps_done + it) % kRefresh) == 0 || (a.ws_valid == 0 && it == 0)));
+    const bool allgrad = a.pred_mode == 2 || ((PRUNE != 0) && (((item(kItemSteps) + it) % kRefresh) == 0 || (it == 0 && item(kItemWsValid) == 0)));
     // Term masks (term_anchor_masks, houv_math.h): a term that provably loses its metric's min is not computed -- no search, no
     // selection, no sums, no rescans; its remembered NNs stay as they are (an older neighbour is still an attained bound).  The
     // proof also settles the prediction: where B's term is dropped A is the winner, and the other way round.  Workgroup-uniform.
@@ -551,7 +652,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       if constexpr (PRUNE) {
         tile_boxes<BLOCK, Q, TS>(mx, my, mz, N, npad / kPad, sm.mbox);   // read by sweep B after the next barriers, and by sweep A's
                                                                          // group cull: each wave its own lanes' entries
-        pruned_now = (a.ws_valid != 0) || (it > 0);
+        pruned_now = (it > 0) || (item(kItemWsValid) != 0);
       }
       if (need_a != 0u) {   // none of A's terms needed: no walk, no selection, no sums (the move and the boxes above are for sweep B)
         if (pruned_now) {
@@ -560,7 +661,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
                                                 need_a, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist), fresh(a.cull_stats));
         } else {
           sweep<Q, NMET>(sm.tgt, mpad / kTrk, mx, my, mz, best, btile);
-          if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
+          if (a.stats && (tid_x() & 63) == 0) atomicAdd(&a.stats[3], 1ull);
         }
         // ---- epilogue A: selection, S of every needed metric, G/GP of the predicted-A metrics; one barrier ----
         unsigned sel[NMET];
@@ -582,7 +683,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         const float4 v = (i < M) ? sm.tgt[i] : make_float4(0.f, 0.f, 0.f, 0.f);
         tx[k] = v.x; ty[k] = v.y; tz[k] = v.z;
       }
-      const bool pruned_now = (PRUNE != 0) && ((a.ws_valid != 0) || (it > 0));
+      const bool pruned_now = (PRUNE != 0) && ((it > 0) || (item(kItemWsValid) != 0));
       // The barriers between B's S and B's G / GP: once with B's sweep state alive around them, once without (need_b is
       // workgroup-uniform, so all waves meet in the same pair).  Written twice so that B's minima are scoped to the branch that
       // computes them: as values merged after a skipped sweep they were carried around the iteration loop, in spilled VGPRs.
@@ -603,7 +704,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
                                                 need_b, sm.st, ws_res, best, btile, a.stats, fresh(a.walk_hist), fresh(a.cull_stats));
         } else {
           sweep<Q, NMET>(sm.mov, npad / kTrk, tx, ty, tz, best, btile);
-          if (a.stats && (tid & 63) == 0) atomicAdd(&a.stats[3], 1ull);
+          if (a.stats && (tid_x() & 63) == 0) atomicAdd(&a.stats[3], 1ull);
         }
         // ---- epilogue B: selection and S first; then the winners are known to every thread ----
         unsigned sel[NMET];
@@ -637,13 +738,13 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     __builtin_amdgcn_wave_barrier();
 
     // ---- per-hypothesis scalar tail: loss, closed-form gradient, Adam, next pose ----
-    if (kAdamTid != 0 && tid == kAdamTid && it + 1 < a.n_iters) {   // next iteration's Adam scalars, while thread 0 works below
-      const int step = a.steps_done + it + 2;
+    if (kAdamTid != 0 && tid_x() == kAdamTid && it + 1 < iw[kItemIters]) {   // next iteration's Adam scalars, while thread 0 works below
+      const int step = iw[kItemSteps] + it + 2;
       const AdamScalars asc = adam_scalars(step, fresh(a.lr), fresh(a.beta1), fresh(a.beta2));
       sm.adam[(step & 1) * 2 + 0] = asc.step_size;
       sm.adam[(step & 1) * 2 + 1] = asc.bc2_sqrt;
     }
-    if (tid == 0) {
+    if (tid_x() == 0) {
       const int k_full = fresh(a.k_full), k_view = fresh(a.k_view);
       const float loss_scale = fresh(a.loss_scale);
       const double lr = fresh(a.lr), beta1 = fresh(a.beta1), beta2 = fresh(a.beta2), eps = fresh(a.eps);
@@ -652,8 +753,8 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
       load_pose(f, sm.pose);        // the forward of the current parameters, kept from the end of the previous tail / the prologue
       TailLoss r;
       solve_tail_loss<NMET>(sm.acc, kAccStride, f, k_full, k_view, loss_scale, trans_mode, r);
-      if (it == a.n_iters - 1)
-        store_outputs(a.out_score, a.out_loss, a.out_R, a.out_T, a.out_grad, a.out_cd, inst, f, r);
+      if (iw[kItemSteps] + it == fresh(a.steps_done) + fresh(a.n_iters) - 1)   // the stage's last iteration (a launch's: its own last)
+        store_outputs(a.out_score, a.out_loss, a.out_R, a.out_T, a.out_grad, a.out_cd, iw[kItemInst], f, r);
       if constexpr (PRUNE != 0) {
         // every term computed in this iteration renews its record: its value here, its pose is this iteration's (sm.pose until
         // the store below); a dropped term's record stays as it is
@@ -663,7 +764,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
           if ((need_a >> m) & 1u) sm.anchor[2 * m + 1] = r.cd[m][1];
         }
       }
-      const int step = a.steps_done + it + 1;
+      const int step = iw[kItemSteps] + it + 1;
       const AdamScalars asc{sm.adam[(step & 1) * 2 + 0], sm.adam[(step & 1) * 2 + 1]};
       solve_tail_step(r.g, sm.state, a.f64_params, asc, beta1, beta2, eps, angle_base, trans_mode, f);
       if constexpr (PRUNE != 0) {
@@ -671,7 +772,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         // one (its eight cd are outputs) and always under pred_mode 2; in between term_anchor_masks drops what the records and the
         // pose just stepped to prove unnecessary (for at most kTermMaxAge iterations in a row where that is set).
         unsigned next = kAllMet | (kAllMet << 4), ages = 0u;
-        const bool all_next = fresh(a.pred_mode) == 2 || it + 2 >= a.n_iters;
+        const bool all_next = fresh(a.pred_mode) == 2 || it + 2 >= iw[kItemIters];
         if (!all_next) {
           const unsigned have = need_b | (need_a << 4);
           float* stale = reinterpret_cast<float*>(sm.tbox) + 3;
@@ -703,7 +804,7 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
         }
       }
       store_pose(sm.pose, f);
-      if (kAdamTid == 0 && it + 1 < a.n_iters) {                       // single-wave workgroups: no other wave to do it
+      if (kAdamTid == 0 && it + 1 < iw[kItemIters]) {                       // single-wave workgroups: no other wave to do it
         const AdamScalars nxt = adam_scalars(step + 1, lr, beta1, beta2);
         sm.adam[((step + 1) & 1) * 2 + 0] = nxt.step_size;
         sm.adam[((step + 1) & 1) * 2 + 1] = nxt.bc2_sqrt;
@@ -713,31 +814,82 @@ __global__ __launch_bounds__(BLOCK, (Q == 1 ? 8 : 4)) void solve_kernel(SolveArg
     // every thread's move of the next iteration.  It also ends this iteration's reads of sm.mov (rescans of direction B) before the next move overwrites it.
     __syncthreads();
   }
-  if (tid_x() < 24) a.state[(size_t)inst * 24 + tid_x()] = sm.state[tid_x()];   // (the prologue's address is not kept alive)
-  if (a.stats) {
-    const unsigned long long dc = __builtin_amdgcn_s_memtime() - clk0, dr = __builtin_amdgcn_s_memrealtime() - rt0;
-    if (tid == 0) {
-      atomicAdd(&a.stats[4], dc);
-      atomicAdd(&a.stats[5], dr);
-    }
+  if (tid_x() < 24) a.state[(size_t)item(kItemInst) * 24 + tid_x()] = sm.state[tid_x()];   // (the prologue's address is not kept alive)
+  if (a.stats && tid_x() == 0) {
+    const unsigned long long clk0 = (unsigned long long)(unsigned)iw[kItemClk] | ((unsigned long long)(unsigned)iw[kItemClk + 1] << 32);
+    const unsigned long long rt0 = (unsigned long long)(unsigned)iw[kItemClk + 2] | ((unsigned long long)(unsigned)iw[kItemClk + 3] << 32);
+    atomicAdd(&a.stats[4], __builtin_amdgcn_s_memtime() - clk0);
+    atomicAdd(&a.stats[5], __builtin_amdgcn_s_memrealtime() - rt0);
+  }
+  if (!fresh(a.sched_ws)) break;
+  // Producer side of the hand-off: plain stores (state above, the NN records in the epilogues) -> every storing wave waits for
+  // its stores -> workgroup barrier -> one lane: agent release, wait, relaxed agent store of done[h].  The barrier is also the
+  // one between this item's last LDS access and the next item's prologue.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid_x() == 0) {
+    const int t = sm.ctl[1], c = t / ninst;   // this item's ticket is still there: the next one is drawn below this
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(a.sched_ws + 4 + (t - c * ninst), c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  }
+  if (fresh(a.sched) && tid_x() == 0) {
+    unsigned long long* s = fresh(a.sched) + 4 * xcc_id();
+    const int* ctl = carve(smem_raw, a.N, a.M, BLOCK, PRUNE ? BLOCK * Q : 0, kPad).ctl;
+    const unsigned long long t0 = (unsigned long long)(unsigned)ctl[2] | ((unsigned long long)(unsigned)ctl[3] << 32);
+    const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+    atomicAdd(s + 0, (unsigned long long)ctl[4]);
+    atomicAdd(s + 1, t1 - t0);
+    atomicMin(s + 2, t0);
+    atomicMax(s + 3, t1);
   }
 }
 
-template <int BLOCK, int Q, int PRUNE>
-int launch(const SolveArgs& a, int use_views, hipStream_t s) {
-  const size_t bytes = smem_bytes(a.N, a.M, BLOCK, PRUNE, Q);
-  const int grid = a.P * a.K;
-  hipError_t e;
-  if (use_views) {
-    e = hipFuncSetAttribute((const void*)solve_kernel<BLOCK, Q, 4, PRUNE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error("houv_solve_iterate: cannot reserve %zu B of LDS: %s", bytes, hipGetErrorString(e)); return 0; }
-    solve_kernel<BLOCK, Q, 4, PRUNE><<<grid, BLOCK, bytes, s>>>(a);
-  } else {
-    e = hipFuncSetAttribute((const void*)solve_kernel<BLOCK, Q, 1, PRUNE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error("houv_solve_iterate: cannot reserve %zu B of LDS: %s", bytes, hipGetErrorString(e)); return 0; }
-    solve_kernel<BLOCK, Q, 1, PRUNE><<<grid, BLOCK, bytes, s>>>(a);
+// Workgroups of a stage's persistent grid: what the chip holds at once (never more than there are hypotheses);
+// houv_debug_set("solve_max_workgroups") caps it for the tests.
+template <typename Kernel>
+int stage_grid(Kernel kernel, const SolveArgs& a, int block, size_t bytes, const char* who) {
+  int dev = 0, cus = 0, per_cu = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, bytes);
+  if (e != hipSuccess || cus < 1 || per_cu < 1) {
+    set_error("%s: cannot size the persistent grid (%d CUs x %d workgroups): %s", who, cus, per_cu, hipGetErrorString(e));
+    return 0;
   }
-  return check_launch("houv_solve_iterate") ? 1 : 0;
+  long long grid = (long long)cus * per_cu;
+  if (grid > (long long)a.P * a.K) grid = (long long)a.P * a.K;
+  const int cap = g_debug.max_workgroups.load();
+  if (cap > 0 && grid > cap) grid = cap;
+  // every workgroup draws one ticket past the last item
+  if (sched_items64(a.P * a.K, a.n_iters, a.chunk_iters) + grid > 0x7fffffffLL) {
+    set_error("%s: too many (hypothesis, chunk) items for one stage", who);
+    return 0;
+  }
+  return (int)grid;
+}
+
+template <typename Kernel>
+int launch_kernel(Kernel kernel, const SolveArgs& a, int block, size_t bytes, hipStream_t s, const char* who) {
+  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) { set_error("%s: cannot reserve %zu B of LDS: %s", who, bytes, hipGetErrorString(e)); return 0; }
+  int grid = a.P * a.K;
+  if (a.sched_ws) {
+    grid = stage_grid(kernel, a, block, bytes, who);
+    if (grid < 1) return 0;
+    e = hipMemsetAsync(a.sched_ws, 0, (4 + (size_t)a.P * a.K) * sizeof(int), s);
+    if (e != hipSuccess) { set_error("%s: cannot zero sched_ws: %s", who, hipGetErrorString(e)); return 0; }
+  }
+  kernel<<<grid, block, bytes, s>>>(a);
+  return check_launch(who) ? 1 : 0;
+}
+
+template <int BLOCK, int Q, int PRUNE>
+int launch(const SolveArgs& a, int use_views, hipStream_t s, const char* who) {
+  const size_t bytes = smem_bytes(a.N, a.M, BLOCK, PRUNE, Q);
+  if (use_views) return launch_kernel(solve_kernel<BLOCK, Q, 4, PRUNE>, a, BLOCK, bytes, s, who);
+  return launch_kernel(solve_kernel<BLOCK, Q, 1, PRUNE>, a, BLOCK, bytes, s, who);
 }
 
 }  // namespace
@@ -827,17 +979,28 @@ int houv::solve_check_args(const char* who, const SolveCommon& a, int use_views)
   return 2;
 }
 
+// stage: houv_solve_stage[_pruned] (chunk_iters and sched_ws are looked at); otherwise one workgroup per hypothesis
 static int solve_dispatch(const houv::SolveCommon& c, int use_views, short* nn_ws, int ws_valid, int ws_stride, bool prune,
-                          void* stream, const char* who) {
+                          void* stream, const char* who, bool stage = false, int chunk_iters = 0, int32_t* sched_ws = nullptr) {
   using namespace houv;
   const int ok = solve_check_args(who, c, use_views);
   if (ok < 2) return ok;
+  if (stage && chunk_iters < 1) {
+    set_error("%s: chunk_iters must be >= 1, got %d", who, chunk_iters);
+    return 0;
+  }
+  if (stage && (!sched_ws || ((uintptr_t)sched_ws & 3))) {
+    set_error("%s: sched_ws must be a 4-byte aligned int32 [4 + P*K] on the device", who);
+    return 0;
+  }
   const int N = c.N, M = c.M;
   // pred_mode / stats are diagnostics set through houv_debug_set(), never through the environment.
   SolveArgs a{c, nn_ws, ws_valid, ws_stride, g_debug.pred_mode.load(),
               reinterpret_cast<unsigned long long*>(g_debug.stats.load()),
               reinterpret_cast<unsigned long long*>(g_debug.walk_hist.load()),
-              reinterpret_cast<unsigned long long*>(g_debug.cull_stats.load())};
+              reinterpret_cast<unsigned long long*>(g_debug.cull_stats.load()),
+              stage ? sched_ws : nullptr, stage ? chunk_iters : 0,
+              reinterpret_cast<unsigned long long*>(g_debug.sched.load())};
   hipStream_t s = (hipStream_t)stream;
   const int mx = N > M ? N : M;
   int block = 0, q = 0, mode = 0;
@@ -859,15 +1022,15 @@ static int solve_dispatch(const houv::SolveCommon& c, int use_views, short* nn_w
   // one instantiation per row of the variant table (houv_solve_variant), x {views, no views}, x {brute force, pruned}
 #define HOUV_GO(B_, Q_)                                                          \
   if (block == B_ && q == Q_) {                                                  \
-    if (mode == 2) return launch<B_, Q_, ((B_ >= 256 && Q_ >= 2) ? 2 : 0)>(a, use_views, s);    \
-    return launch<B_, Q_, 0>(a, use_views, s);                                   \
+    if (mode == 2) return launch<B_, Q_, ((B_ >= 256 && Q_ >= 2) ? 2 : 0)>(a, use_views, s, who);    \
+    return launch<B_, Q_, 0>(a, use_views, s, who);                                   \
   }
   if (mx <= 2048) {
     HOUV_GO(64, 1) HOUV_GO(128, 1) HOUV_GO(256, 1) HOUV_GO(256, 2) HOUV_GO(256, 3) HOUV_GO(256, 4)
     HOUV_GO(512, 3) HOUV_GO(512, 4)
   } else {
-    if (block == 1024 && q == 3) return mode == 3 ? launch<1024, 3, 3>(a, use_views, s) : launch<1024, 3, 0>(a, use_views, s);
-    if (block == 1024 && q == 4) return mode == 3 ? launch<1024, 4, 3>(a, use_views, s) : launch<1024, 4, 0>(a, use_views, s);
+    if (block == 1024 && q == 3) return mode == 3 ? launch<1024, 3, 3>(a, use_views, s, who) : launch<1024, 3, 0>(a, use_views, s, who);
+    if (block == 1024 && q == 4) return mode == 3 ? launch<1024, 4, 3>(a, use_views, s, who) : launch<1024, 4, 0>(a, use_views, s, who);
   }
 #undef HOUV_GO
   set_error("%s: no kernel variant <%d,%d>", who, block, q);
@@ -893,4 +1056,26 @@ extern "C" int houv_solve_iterate_pruned(const float* src, const float* tgt, int
   const houv::SolveCommon a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
                             lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd};
   return solve_dispatch(a, use_views, (short*)nn_ws, ws_valid, ws_stride, true, stream, "houv_solve_iterate_pruned");
+}
+
+extern "C" int houv_solve_stage(const float* src, const float* tgt, int P, int N, int M, int K, double* state, int steps_done,
+                                int n_iters, int angle_base, int trans_mode, int use_views, int f64_params, int k_full,
+                                int k_view, double lr, double beta1, double beta2, double eps, float loss_scale,
+                                float* out_score, float* out_loss, float* out_R, float* out_T, float* out_grad, float* out_cd,
+                                int chunk_iters, int32_t* sched_ws, void* stream) {
+  const houv::SolveCommon a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
+                            lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd};
+  return solve_dispatch(a, use_views, nullptr, 0, 0, false, stream, "houv_solve_stage", true, chunk_iters, sched_ws);
+}
+
+extern "C" int houv_solve_stage_pruned(const float* src, const float* tgt, int P, int N, int M, int K, double* state,
+                                       int steps_done, int n_iters, int angle_base, int trans_mode, int use_views,
+                                       int f64_params, int k_full, int k_view, double lr, double beta1, double beta2,
+                                       double eps, float loss_scale, float* out_score, float* out_loss, float* out_R,
+                                       float* out_T, float* out_grad, float* out_cd, int16_t* nn_ws, int ws_valid,
+                                       int ws_stride, int chunk_iters, int32_t* sched_ws, void* stream) {
+  const houv::SolveCommon a{src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, f64_params, k_full, k_view,
+                            lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd};
+  return solve_dispatch(a, use_views, (short*)nn_ws, ws_valid, ws_stride, true, stream, "houv_solve_stage_pruned", true,
+                        chunk_iters, sched_ws);
 }

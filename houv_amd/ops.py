@@ -95,12 +95,13 @@ def pose_forward(params, angle_base, trans_mode=0, src=None):
 
 def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                       k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad=None,
-                      out_cd=None, nn_ws=None, ws_valid=0, large=False):
+                      out_cd=None, nn_ws=None, ws_valid=0, large=False, chunk_iters=None, sched_ws=None):
     """The C-ABI call itself, caller-allocated outputs (``houv_solve_iterate`` / ``houv_solve_iterate_pruned`` when a
     workspace is given / ``houv_solve_iterate_large`` with ``large``): what ``torch.ops.houv.solve_iterate[_pruned|_large]``
     bind.  ``state`` [P*K,24] fp64 (and ``nn_ws``) are updated in place; the out_* tensors receive the LAST forward's values.
-    Returns 1."""
-    _lib.require_gpu(src, tgt, state, out_score, out_loss, out_R, out_T, out_grad, out_cd, nn_ws)
+    With ``sched_ws`` (solve_sched_workspace) the call is ``houv_solve_stage[_pruned]``: ``n_iters`` is a whole stage, run in one
+    launch as items of ``chunk_iters`` iterations.  Returns 1."""
+    _lib.require_gpu(src, tgt, state, out_score, out_loss, out_R, out_T, out_grad, out_cd, nn_ws, sched_ws)
     _want(src, _F32, "src"); _want(tgt, _F32, "tgt"); _want(state, _F64, "state")
     P, N, _ = src.shape
     M = tgt.shape[1]
@@ -121,9 +122,23 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
               _lib.ptr(out_loss), _lib.ptr(out_R), _lib.ptr(out_T), _lib.ptr(out_grad), _lib.ptr(out_cd))
     if large and nn_ws is not None:
         raise _lib.HouvHipError("solve_iterate: the large-cloud kernel is a brute-force sweep and takes no workspace")
+    stage = sched_ws is not None
+    if stage:
+        if large:
+            raise _lib.HouvHipError("solve_iterate: the large-cloud kernel has no stage form")
+        if sched_ws.dtype != torch.int32 or sched_ws.numel() < 4 + n:
+            raise _lib.HouvHipError(f"solve_iterate: sched_ws must hold {4 + n} int32 (ops.solve_sched_workspace)")
+        sched = (int(chunk_iters), _lib.ptr(sched_ws))
     with torch.cuda.device(src.device):
         if large:
             ok = _lib.load().houv_solve_iterate_large(*common, _lib.stream_of(src))
+        elif stage and nn_ws is None:
+            ok = _lib.load().houv_solve_stage(*common, *sched, _lib.stream_of(src))
+        elif stage:
+            if nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16) or not nn_ws.is_contiguous():
+                raise _lib.HouvHipError("solve_iterate: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
+            ok = _lib.load().houv_solve_stage_pruned(*common, _lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2], *sched,
+                                                     _lib.stream_of(src))
         elif nn_ws is None:
             ok = _lib.load().houv_solve_iterate(*common, _lib.stream_of(src))
         else:   # exact pruned search: nn_ws int16 [P*K, 16, stride] (solve_workspace) persists between chunked launches
@@ -131,7 +146,8 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
                 raise _lib.HouvHipError("solve_iterate: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
             ok = _lib.load().houv_solve_iterate_pruned(*common, _lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2],
                                                        _lib.stream_of(src))
-    _lib.check(ok, "houv_solve_iterate" + ("_large" if large else "_pruned" if nn_ws is not None else ""))
+    _lib.check(ok, ("houv_solve_stage" if stage else "houv_solve_iterate") +
+               ("_large" if large else "_pruned" if nn_ws is not None else ""))
     return 1
 
 
@@ -153,11 +169,17 @@ def solve_workspace(n_hypotheses, N, M, device):
     return torch.empty((int(n_hypotheses), 16, stride), dtype=torch.int16, device=device)
 
 
+def solve_sched_workspace(n_hypotheses, device):
+    """Scheduling workspace of houv_solve_stage[_pruned] for n hypotheses: int32 [4 + n] (ticket counter, status word, two spares,
+    done[h]).  One per stage in flight; the call zeroes it.  Word 1 is the status: non-zero after the launch = the stage failed."""
+    return torch.empty(4 + int(n_hypotheses), dtype=torch.int32, device=device)
+
+
 def solve_iterate(src, tgt, state, K, *, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                   k_view, lr, loss_scale, betas=(0.9, 0.999), eps=1e-8, want_grad=False, want_cd=False, nn_ws=None,
-                  ws_valid=False, large=False):
+                  ws_valid=False, large=False, chunk_iters=None, sched_ws=None):
     """One launch of the fused HOUV loop (houv_solve_iterate; ``large``: houv_solve_iterate_large, clouds of up to 16384
-    points).  ``state`` [P*K,24] fp64 is updated in place.
+    points; with ``sched_ws``: houv_solve_stage, a whole stage as items of ``chunk_iters`` iterations).  ``state`` [P*K,24] fp64 is updated in place.
     Returns dict(score[P*K], loss[P*K], R[P*K,3,3], T[P*K,3][, grad[P*K,8]][, cd[P*K,8]]) of the LAST forward."""
     _lib.require_gpu(src, tgt, state)
     dev = src.device
@@ -170,7 +192,8 @@ def solve_iterate(src, tgt, state, K, *, steps_done, n_iters, angle_base, trans_
         out["cd"] = torch.empty((n, 8), dtype=_F32, device=dev)
     solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                       k_view, lr, betas[0], betas[1], eps, loss_scale, out["score"], out["loss"], out["R"], out["T"],
-                      out.get("grad"), out.get("cd"), nn_ws, -1 if ws_valid == "verify" else int(bool(ws_valid)), large=large)
+                      out.get("grad"), out.get("cd"), nn_ws, -1 if ws_valid == "verify" else int(bool(ws_valid)), large=large,
+                      chunk_iters=chunk_iters, sched_ws=sched_ws)
     return out
 
 

@@ -11,11 +11,34 @@ import torch
 from . import ops
 
 RETRY_THRESHOLD = 0.030      # houv.py:156, train_utils.py:494 (strict >)
-ITERS_PER_LAUNCH = 50        # bound single-launch duration; state round-trips through HBM (192 B/hypothesis)
+ITERS_PER_LAUNCH = 50        # iterations per item of a stage (houv_solve_stage: one launch per stage, whose persistent grid
+                             # draws (hypothesis, chunk) tickets), and per launch where run_stage launches chunk by chunk;
+                             # state round-trips through HBM (192 B/hypothesis)
 
 # bench.py sets this to a list to collect (start_event, end_event, hypotheses, iterations, N, M, use_views, pruned, first) per
-# houv_solve_iterate[_pruned|_large] launch: HIP events recorded on the stream the kernel is launched on.
+# houv_solve_iterate[_pruned|_large] / houv_solve_stage[_pruned] launch: HIP events recorded on the stream the kernel is launched on.
 LAUNCH_LOG = None
+
+# Status words of the houv_solve_stage launches not yet looked at: (sched_ws, event recorded behind the launch).  Non-zero = a
+# workgroup's bounded wait for the previous chunk of its hypothesis ran out and the stage ended early.  Reading a word needs the
+# launch finished, so run_stage only files it here; check_stage_status() reads the finished ones where the caller has synchronised
+# anyway (best_of_k_with_retry does, after each of its host syncs).
+_STAGE_STATUS = []
+
+
+def check_stage_status(wait=False):
+    """Raise if a finished houv_solve_stage launch reported a failed hand-off (``wait``: finish the pending launches first)."""
+    pending = []
+    for ws, ev in _STAGE_STATUS:
+        if wait:
+            ev.synchronize()
+        if not ev.query():
+            pending.append((ws, ev))
+        elif int(ws[1].item()) != 0:
+            _STAGE_STATUS.clear()
+            raise RuntimeError("houv_solve_stage: a workgroup's wait for the previous chunk of its hypothesis ran out of time "
+                               f"(status {int(ws[1].item())}); the stage's results are not valid")
+    _STAGE_STATUS[:] = pending
 
 # the 26 non-zero {-1,0,1}^3 axes in the reference's loop order (houv.py:44-51)
 LATTICE_AXES = np.array([(x, y, z) for x in (-1, 0, 1) for y in (-1, 0, 1) for z in (-1, 0, 1)
@@ -410,6 +433,27 @@ def run_stage(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views
         nn_ws = ops.solve_workspace(n, N, tgt.shape[1], dev)
     done, out = 0, None
     last_params = None
+    if not iters_per_launch and not want_last_params:
+        # the whole stage in ONE launch: items of ITERS_PER_LAUNCH iterations, bit for bit the launches of the loop below
+        sched_ws = ops.solve_sched_workspace(n, dev)
+        if LAUNCH_LOG is not None:
+            ev0 = torch.cuda.Event(enable_timing=True)
+            ev1 = torch.cuda.Event(enable_timing=True)
+            ev0.record(torch.cuda.current_stream(dev))
+        out = ops.solve_iterate(src, tgt, state, K, steps_done=0, n_iters=n_iters, angle_base=angle_base,
+                                trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
+                                k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad, want_cd=want_cd, nn_ws=nn_ws,
+                                ws_valid="verify" if pruned == "verify" else False, chunk_iters=step, sched_ws=sched_ws)
+        if LAUNCH_LOG is not None:
+            ev1.record(torch.cuda.current_stream(dev))
+            LAUNCH_LOG.append((ev0, ev1, n, n_iters, N, tgt.shape[1], bool(use_views), nn_ws is not None, True))
+        if src.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            if len(_STAGE_STATUS) >= 64:
+                check_stage_status(wait=True)
+            _STAGE_STATUS.append((sched_ws, ev))
+        return out, state
     while done < n_iters:
         it = min(step, n_iters - done)
         if want_last_params:
@@ -460,6 +504,7 @@ def best_of_k_with_retry(stage_fn, src, tgt):
     score, R, T = stage_fn(src, tgt, 0)
     best, _ = score.topk(1, dim=1, largest=False, sorted=True)          # NaN hypotheses sort last
     retry = torch.nonzero(best[:, 0] > RETRY_THRESHOLD).reshape(-1)
+    check_stage_status()
     if retry.numel() > 0:
         s_add, t_add = src[retry].contiguous(), tgt[retry].contiguous()
         for sub, whole in ((s_add, src), (t_add, tgt)):        # pairs picked out of a sorted batch are sorted: the three retry
@@ -492,6 +537,7 @@ def best_of_k_with_retry(stage_fn, src, tgt):
             score[ge] = score_a[flag]
             T[ge] = T_a[flag]
             best[ge] = best_a[flag]
+        check_stage_status()                                           # the nonzero() above waited for the retry stages
     _, k = score.topk(1, dim=1, largest=False, sorted=True)
     pick = k[:, 0]
     rows = torch.arange(B, device=score.device)

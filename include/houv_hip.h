@@ -125,6 +125,41 @@ int houv_solve_iterate_pruned(const float* src, const float* tgt, int P, int N, 
                               float* out_grad, float* out_cd,
                               int16_t* nn_ws, int ws_valid, int ws_stride, void* stream);
 
+/* A whole STAGE of the fused loop in one launch (what houv_amd.solver runs for a stage): the arguments of houv_solve_iterate /
+ * houv_solve_iterate_pruned, with n_iters the whole stage, plus
+ *   chunk_iters        length of an item in iterations (>= 1; the stage's last item may be shorter)
+ *   sched_ws[4 + P*K]  int32 scheduling workspace on the device, 4-byte aligned, one per stage in flight; the call zeroes it
+ *                      on `stream`.  [0] ticket counter, [1] status, [2..3] spare, [4 + h] chunks of hypothesis h finished.
+ * A persistent grid -- as many workgroups as the chip holds at once, at most P*K -- draws tickets from sched_ws[0]; ticket t is
+ * the item (chunk t / (P*K), hypothesis t % (P*K)), so a stage has one tail of one item and no part of the chip waits for
+ * another.  An item is exactly what houv_solve_iterate[_pruned] does for one hypothesis in a launch of chunk_iters iterations at
+ * steps_done + chunk * chunk_iters (pruned: ws_valid || chunk > 0): state, outputs and nn_ws are BIT FOR BIT those of separate
+ * launches of chunk_iters.  The out_* values are stored on the stage's last iteration only.
+ * Status: a workgroup that starts chunk c > 0 of a hypothesis checks that chunk c - 1 is finished, and waits where it is still
+ * running; the wait is bounded by time, and a wait that runs out sets sched_ws[1] non-zero and ends the launch early -- the
+ * caller reads sched_ws[1] after synchronising and must treat non-zero as a failed stage.
+ * Returns 1 at once when P == 0; 0 with houv_last_error() set when chunk_iters < 1, sched_ws is null or misaligned, or a check of
+ * houv_solve_iterate[_pruned] fails.  houv_debug_set("solve_max_workgroups", n) caps the grid (0 = off; tests);
+ * houv_debug_set("solve_sched", address of 32 uint64 on the device) collects per XCD: items run, sum of its workgroups' durations,
+ * earliest start and latest end in 100-MHz ticks (the caller presets the minima to all ones).  No counterpart in the reference. */
+int houv_solve_stage(const float* src, const float* tgt, int P, int N, int M, int K,
+                     double* state, int steps_done, int n_iters,
+                     int angle_base, int trans_mode, int use_views, int f64_params,
+                     int k_full, int k_view,
+                     double lr, double beta1, double beta2, double eps, float loss_scale,
+                     float* out_score, float* out_loss, float* out_R, float* out_T,
+                     float* out_grad, float* out_cd,
+                     int chunk_iters, int32_t* sched_ws, void* stream);
+int houv_solve_stage_pruned(const float* src, const float* tgt, int P, int N, int M, int K,
+                            double* state, int steps_done, int n_iters,
+                            int angle_base, int trans_mode, int use_views, int f64_params,
+                            int k_full, int k_view,
+                            double lr, double beta1, double beta2, double eps, float loss_scale,
+                            float* out_score, float* out_loss, float* out_R, float* out_T,
+                            float* out_grad, float* out_cd,
+                            int16_t* nn_ws, int ws_valid, int ws_stride,
+                            int chunk_iters, int32_t* sched_ws, void* stream);
+
 /* Fused loop for LARGE clouds (what houv_amd.solver runs for 4097..16384 points): the same arguments, outputs and arithmetic
  * contract as houv_solve_iterate, for clouds that do not fit in LDS.  Neither cloud is resident: every workgroup (1024 threads,
  * one hypothesis) holds 4096 query points at a time in registers and streams the other cloud through a double-buffered LDS
