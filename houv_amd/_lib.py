@@ -102,6 +102,8 @@ _SIGNATURES = {
     "houv_ef_expand_backward": (ctypes.c_int, [_c_f, _int, _c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _int, _c_f, _c_f, _int, _c_f,
                                                _int, _c_f, _c_f, _c_f, _c_f, ctypes.c_longlong, _c_f]),
     "houv_ef_expand_backward_workspace_bytes": (ctypes.c_longlong, [_int] * 5),
+    "houv_cd_loss_backward": (ctypes.c_int, [_c_f] * 8 + [_int, _int, _int, _c_f, _c_f, ctypes.c_longlong, _c_f]),
+    "houv_cd_loss_backward_workspace_bytes": (ctypes.c_longlong, [_int, _int, _int]),
     "houv_pose_forward": (ctypes.c_int,[_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 

@@ -21,9 +21,10 @@ void set_error(const char* fmt, ...);
 struct SolveCommon;
 __attribute__((visibility("hidden"))) int solve_check_args(const char* who, const SolveCommon& a, int use_views);
 // The index step of the ordered scatter (defined in pointops_group.hip): a stable counting sort of keys[B][M] (each in [0, N)) by
-// destination, giving the CSR inverse offsets[B][N+1], order[B][M] with the sources of a destination in ascending m.  Internal.
+// destination, giving the CSR inverse offsets[B][N+1], order[B][M] with the sources of a destination in ascending m.  A key
+// outside [0, N) is skipped, or with `clamp` taken as the nearest of 0 and N-1.  Internal.
 __attribute__((visibility("hidden"))) bool scatter_index_launch(const int* keys, int B, int N, int M, int* offsets, int* order,
-                                                                hipStream_t stream);
+                                                                hipStream_t stream, bool clamp = false);
 inline bool check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

@@ -99,14 +99,17 @@ __global__ __launch_bounds__(256) void three_interpolate_kernel(const float* __r
 // walked in chunks of 1024 in ascending m.  Inside a wave equal keys are ranked by a readlane/ballot loop (as many turns
 // as the wave holds distinct keys; ONE when all are equal); the 16 waves of a chunk then take their base from the cursor one
 // after the other, the lowest lane of each key advancing it by the wave's count.  The sort is exact integer work: no atomics
-// decide an order.  Keys outside [0,N) are skipped.
+// decide an order.  Keys outside [0,N) are skipped; with CLAMP they are taken as the nearest of 0 and N-1 instead (the lists
+// of houv_cd_loss_backward, which must not lose a source).
 constexpr int kScatThreads = 1024;
 constexpr int kScatWaves = kScatThreads / 64;
 constexpr int kScatKeys = 8192;            // 32 KiB of LDS cursors
 constexpr int kScatPer = kScatKeys / kScatThreads;
 
+template <bool CLAMP>
 __global__ __launch_bounds__(kScatThreads) void scatter_index_kernel(const int* __restrict__ idx, int N, int M,
                                                                      int* __restrict__ offsets, int* __restrict__ order) {
+  auto key_of = [&](int v) { return CLAMP ? min(max(v, 0), N - 1) : v; };
   __shared__ int s_cur[kScatKeys];
   __shared__ int s_part[kScatWaves];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(kScatThreads) void scatter_index_kernel(const int* 
     for (int i = tid; i < kScatKeys; i += kScatThreads) s_cur[i] = 0;
     __syncthreads();
     for (int m = tid; m < M; m += kScatThreads) {
-      const int key = key_in[m] - k0;
+      const int key = key_of(key_in[m]) - k0;
       if ((unsigned)key < (unsigned)nk) atomicAdd(&s_cur[key], 1);
     }
     __syncthreads();
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(kScatThreads) void scatter_index_kernel(const int* 
     // place the sources, 1024 at a time in ascending m
     for (int m0 = 0; m0 < M; m0 += kScatThreads) {
       const int m = m0 + tid;
-      const int key = m < M ? key_in[m] - k0 : -1;
+      const int key = m < M ? key_of(key_in[m]) - k0 : -1;
       const bool valid = (unsigned)key < (unsigned)nk;
       int rank = 0, cnt = 0;
       unsigned long long pend = __ballot(valid);
@@ -220,8 +223,9 @@ unsigned grid_for(size_t total) {
 
 }  // namespace
 
-bool scatter_index_launch(const int* keys, int B, int N, int M, int* offsets, int* order, hipStream_t stream) {
-  scatter_index_kernel<<<B, kScatThreads, 0, stream>>>(keys, N, M, offsets, order);
+bool scatter_index_launch(const int* keys, int B, int N, int M, int* offsets, int* order, hipStream_t stream, bool clamp) {
+  if (clamp) scatter_index_kernel<true><<<B, kScatThreads, 0, stream>>>(keys, N, M, offsets, order);
+  else scatter_index_kernel<false><<<B, kScatThreads, 0, stream>>>(keys, N, M, offsets, order);
   return check_launch("scatter_index_kernel");
 }
 
@@ -272,7 +276,7 @@ extern "C" int houv_scatter_points_grad(const float* grad_out, const int32_t* id
   hipStream_t s = (hipStream_t)stream;
   int* offsets = (int*)workspace;
   int* order = offsets + (size_t)B * ((size_t)N + 1);
-  scatter_index_kernel<<<B, kScatThreads, 0, s>>>(idx, N, M, offsets, order);
+  scatter_index_kernel<false><<<B, kScatThreads, 0, s>>>(idx, N, M, offsets, order);
   if (!check_launch("houv_scatter_points_grad")) return 0;
   const size_t total = (size_t)B * C * N;
   if (S == 1) scatter_sum_kernel<1><<<grid_for(total), 256, 0, s>>>(grad_out, weight_or_null, offsets, order, total, C, N, M, S, grad_features);

@@ -34,6 +34,43 @@ def calc_cd(output, gt, calc_f1=False):
     return (cd_p, cd_t, _f1(dist1, dist2)) if calc_f1 else (cd_p, cd_t)
 
 
+class _CdLossFunction(torch.autograd.Function):
+    """calc_cd(output, gt) as ONE autograd node.  forward: calc_cd's own operations -- the Chamfer
+    launch, then the same torch sqrt, mean and / 2 -- so cd_p and cd_t carry its bits.  backward: one ops.cd_loss_backward, the
+    ordered sums of houv_cd_loss_backward (no float atomics, no zeroed buffer, no [B,N] / [B,M] gradient of the distances).
+    Saved: output, gt, dist1, dist2, idx1, idx2.  gt gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, output, gt):
+        output, gt = output.contiguous(), gt.contiguous()
+        B, M, _ = output.shape
+        N = gt.shape[1]
+        dev = output.device
+        dist1 = torch.empty((B, N), dtype=torch.float32, device=dev)
+        dist2 = torch.empty((B, M), dtype=torch.float32, device=dev)
+        idx1 = torch.empty((B, N), dtype=torch.int32, device=dev)
+        idx2 = torch.empty((B, M), dtype=torch.int32, device=dev)
+        ops.chamfer_forward(gt, output, dist1, dist2, idx1, idx2)
+        cd_p = (torch.sqrt(dist1).mean(1) + torch.sqrt(dist2).mean(1)) / 2
+        cd_t = dist1.mean(1) + dist2.mean(1)
+        ctx.save_for_backward(output, gt, dist1, dist2, idx1, idx2)
+        return cd_p, cd_t
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_p, g_t):
+        return ops.cd_loss_backward(*ctx.saved_tensors, g_p.contiguous(), g_t.contiguous()), None
+
+
+def cd_loss(output, gt):
+    """(cd_p[B], cd_t[B]) of calc_cd(output[B,M,3], gt[B,N,3]), bit for bit, as one autograd node whose gradient with respect to
+    `output` is summed in a fixed order: two backward passes over the same values give the same bits (calc_cd's go through
+    float atomics).  The gradient with respect to the ground truth is not built: a gt that requires one is refused."""
+    if gt.requires_grad:
+        raise ValueError("cd_loss: the gradient with respect to the ground truth is not built (gt.requires_grad)")
+    return _CdLossFunction.apply(output, gt)
+
+
 def calc_cd_percent(output, gt, calc_f1=False, percent=1):
     k = int(output.shape[1] * percent)
     dist1, dist2, _, _ = cd()(gt, output)

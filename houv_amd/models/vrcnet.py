@@ -16,9 +16,10 @@ repository ships no trained weights: tests use seeded ones).  SA_module, SK_SA_m
 (one _SAAttnFunction node per attention block over houv_sa_attn_backward), and so does
 SA_SKN_Res_encoder (section 9.15: each edge-preserve pooling one _EdgePoolFunction node over houv_edge_pool /
 houv_edge_pool_backward, which the inference path shares) and MSAP_SKN_decoder (section 9.16: both EF_expansions through
-_EFExpandFunction over houv_ef_expand / houv_ef_expand_backward, Folding as the same three-part sum with a graph); Model stays
-inference only: the "train" prefix doubles the batch, draws two latent samples and needs the KL / MMD terms (the reference's
-MMD branch also calls a method that does not exist); it raises NotImplementedError.
+_EFExpandFunction over houv_ef_expand / houv_ef_expand_backward, Folding as the same three-part sum with a graph), and so
+does Model (section 9.17): its "train" prefix doubles the batch, draws two latent samples, and sums four Chamfer losses -- each
+one cd_loss node over houv_cd_loss_backward, whose sums are ordered -- with the two KL terms.  The reference's MMD branch calls
+a method that does not exist; it raises NotImplementedError here.
 
 Two things the reference does that are easy to miss and are kept: Linear_ResBlock's ReLU is in place, so its residual branch
 sees relu(feature) and the CALLER's tensor is rectified too -- the decoder receives relu(feat) + generator(z), not feat +
@@ -26,8 +27,11 @@ generator(z); and SA_SKN_Res_encoder's decoder call hard-codes pts_num = [3072, 
 
 Discrete decisions.  ``Model(..., trace={})`` records every one of them, as models/ecg.py does: knn{level}_{i} for each level 1..4
 and each list i, fps1..3, knn_pt1..3, three_nn1..3, knn_exp1 (+ knn_exp1_x, the rows it was computed from) when up_scale >= 2,
-fps_out, topk, knn_exp2 (+ knn_exp2_x) when local_folding is off, plus feat (the PCN encoder's output) and z.  With trace=None
-nothing is recorded or copied."""
+fps_out, topk, knn_exp2 (+ knn_exp2_x) when local_folding is off, plus feat (the PCN encoder's output) and z; the "train"
+prefix adds fps_gt (the sample of the ground truth), q_mu, q_std, p_mu, p_std, global_feat, dl_rec, dl_g and loss1..4, all detached from the step's graph.  With
+trace=None nothing is recorded or copied."""
+import warnings
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -36,7 +40,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..mm3d_pn2 import furthest_point_sample, knn_cross
 from ..model_utils_completion import (Conv1x1, EF_expansion, _LinearFunction, _LinearRowsFunction, _RowGather, _take_rows,
-                                       _weight_grad, calc_cd, calc_emd, gen_grid_up)
+                                       _weight_grad, calc_cd, calc_emd, cd_loss, gen_grid_up)
 from .ecg import EF_encoder, _conv, _lin
 from .pcn import PCN_encoder
 
@@ -415,18 +419,28 @@ class Folding(nn.Module):
 
 
 class Linear_ResBlock(nn.Module):
-    """vrcnet.py:116-127.  The reference's ReLU is in place: the residual branch sees relu(feature) too."""
+    """vrcnet.py:116-127.  The reference's ReLU is in place: the residual branch sees relu(feature) too.
 
-    def __init__(self, input_size=1024, output_size=256):
+    trainable=True: with grad mode on, the same three products through _LinearFunction, the first
+    ReLU and the residual add as torch ops.  The GEMM's epilogue computes (acc + bias) + residual, and so does this path
+    ((acc + bias) from conv2's node, then + the residual branch): the output carries the bits of the inference path.  With grad
+    mode off, or trainable=False, the inference path runs and builds no graph."""
+
+    def __init__(self, input_size=1024, output_size=256, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.conv1 = nn.Linear(input_size, input_size)
         self.conv2 = nn.Linear(input_size, output_size)
         self.conv_res = nn.Linear(input_size, output_size)
 
-    @torch.no_grad()
     def forward(self, feature):
-        r = torch.relu(feature)
-        return _linear(self.conv2, _linear(self.conv1, r, relu=True), residual=_linear(self.conv_res, r))
+        if self.trainable and torch.is_grad_enabled():
+            lin = lambda fc, t, relu: _LinearFunction.apply(t, fc.weight, fc.bias, relu)
+            r = torch.relu(feature)
+            return lin(self.conv2, lin(self.conv1, r, True), False) + lin(self.conv_res, r, False)
+        with torch.no_grad():
+            r = torch.relu(feature)
+            return _linear(self.conv2, _linear(self.conv1, r, relu=True), residual=_linear(self.conv_res, r))
 
 
 class MSAP_SKN_decoder(nn.Module):
@@ -569,37 +583,118 @@ class MSAP_SKN_decoder(nn.Module):
 
 
 class Model(nn.Module):
-    """``Model(args, size_z=128, global_feature_size=1024, trace=None).forward(x[B,3,N], gt=None, prefix="train",
-    mean_feature=None, alpha=None, z=None)`` (vrcnet.py:510-656).  ``args``: layers, knn_list (comma-separated strings),
-    distribution_loss, loss, eval_emd, num_fps, num_points, num_coarse, num_coarse_raw, pk, local_folding, points_label
-    (cfgs/vrcnet_mi355x.yaml).
+    """``Model(args, size_z=128, global_feature_size=1024, trace=None, trainable=False).forward(x[B,3,N], gt=None,
+    prefix="train", mean_feature=None, alpha=None, z=None, eps=None)`` (vrcnet.py:510-656).  ``args``: layers, knn_list
+    (comma-separated strings), distribution_loss, loss, eval_emd, num_fps, num_points, num_coarse, num_coarse_raw, pk,
+    local_folding, points_label (cfgs/vrcnet_mi355x.yaml).
 
     "test": {'result': fine}.  "val": the reference's dictionary out1 (coarse_raw), out2 (fine), cd_p, cd_t, f1, and 'emd' as well
-    when eval_emd is set (the reference computes it and drops it).  "train" raises NotImplementedError: it is out of scope.
+    when eval_emd is set (the reference computes it and drops it).  Both run the inference path, without a graph, under either
+    flag and either grad mode.
+
+    "train" (trainable=True) -> (fine [2B, num_points, 3], loss4_t [2B], total), the reference's tuple
+    with rows of points: the batch doubled with a furthest-point sample of gt, the posterior from x and the prior from that
+    sample, one latent draw from each, the decoder on both, four cd_loss nodes against the doubled gt and the two KL terms.
+    With grad mode on, total.backward() reaches every parameter but conv_s1..3 (the scores only select rows), and two steps
+    from the same state, `eps` and dropout seed give bit-equal gradients.  Under torch.no_grad() the same tuple is computed
+    without a graph: the decoder then runs its inference path, whose two dropouts are the identity, so it is the eval() result
+    (within the fp32 spread between the decoder's two paths).  With the default trainable=False "train" raises
+    NotImplementedError.
 
     The reference draws the latent z = q.rsample() even under "test"; ``z`` (B,size_z), when given, replaces the sample, and
-    with z=None q_mu + softplus(q_std) * randn is drawn on the device (torch's generator: seed it for a repeatable result)."""
+    with z=None q_mu + softplus(q_std) * randn is drawn on the device (torch's generator: seed it for a repeatable result).
+    ``eps`` = (eps_q, eps_p), two (B,size_z) tensors, does the same for the two draws of "train": z_q = q_mu + q_std * eps_q,
+    z_p = p_mu + p_std * eps_p."""
 
-    def __init__(self, args, size_z=128, global_feature_size=1024, trace=None):
+    def __init__(self, args, size_z=128, global_feature_size=1024, trace=None, trainable=False):
         super().__init__()
         layers = [int(i) for i in str(args.layers).split(',')]
         knn_list = [int(i) for i in str(args.knn_list).split(',')]
         self.size_z = size_z
         self.distribution_loss, self.train_loss, self.eval_emd = args.distribution_loss, args.loss, args.eval_emd
         self.trace = trace
-        self.encoder = PCN_encoder(output_size=global_feature_size)
-        self.posterior_infer1 = Linear_ResBlock(input_size=global_feature_size, output_size=global_feature_size)
-        self.posterior_infer2 = Linear_ResBlock(input_size=global_feature_size, output_size=size_z * 2)
-        self.prior_infer = Linear_ResBlock(input_size=global_feature_size, output_size=size_z * 2)
-        self.generator = Linear_ResBlock(input_size=size_z, output_size=global_feature_size)
+        self.trainable = bool(trainable)
+        block = lambda n_in, n_out: Linear_ResBlock(input_size=n_in, output_size=n_out, trainable=trainable)
+        self.encoder = PCN_encoder(output_size=global_feature_size, trainable=trainable)
+        self.posterior_infer1 = block(global_feature_size, global_feature_size)
+        self.posterior_infer2 = block(global_feature_size, size_z * 2)
+        self.prior_infer = block(global_feature_size, size_z * 2)
+        self.generator = block(size_z, global_feature_size)
         self.decoder = MSAP_SKN_decoder(num_fps=args.num_fps, num_fine=args.num_points, num_coarse=args.num_coarse,
                                         num_coarse_raw=args.num_coarse_raw, layers=layers, knn_list=knn_list, pk=args.pk,
-                                        local_folding=args.local_folding, points_label=args.points_label)
+                                        local_folding=args.local_folding, points_label=args.points_label, trainable=trainable)
 
-    @torch.no_grad()
-    def forward(self, x, gt=None, prefix="train", mean_feature=None, alpha=None, z=None):
+    def forward(self, x, gt=None, prefix="train", mean_feature=None, alpha=None, z=None, eps=None):
         if prefix == "train":
-            raise NotImplementedError('VRCNet: the "train" prefix (doubled batch, two latent samples, KL / MMD terms) is not built')
+            if not self.trainable:
+                raise NotImplementedError('VRCNet: the "train" prefix (doubled batch, two latent samples, KL terms) needs '
+                                          'Model(..., trainable=True)')
+            return self._forward_train(x, gt, alpha, eps)
+        with torch.no_grad():
+            return self._forward_infer(x, gt, prefix, z)
+
+    def _forward_train(self, x, gt, alpha, eps):
+        """vrcnet.py:565-641 on rows.  The reference rectifies feat_x and feat_y in place (posterior_infer1's and prior_infer's
+        ReLU act on views of the encoder's output, which torch 2.10 refuses on a chunk view): relu(feat_x) and relu(feat_y)
+        are the values every later use sees, and the gradients flow back through those two ReLUs."""
+        if self.distribution_loss == "MMD":
+            raise NotImplementedError("VRCNet: distribution_loss = 'MMD' is not built (the reference's branch calls mmd_loss2, a "
+                                      "method that does not exist)")
+        if self.distribution_loss != "KLD":
+            raise NotImplementedError("Distribution loss is either MMD or KLD")
+        if self.train_loss != "cd":
+            raise NotImplementedError("Only CD is supported")
+        if gt is None or alpha is None:
+            raise ValueError('VRCNet: the "train" prefix needs gt and alpha')
+        if x.requires_grad:
+            raise ValueError("VRCNet: the gradient with respect to the input cloud is not built (x.requires_grad)")
+        if self.training and not torch.is_grad_enabled():
+            warnings.warn('VRCNet: "train" under torch.no_grad() runs the decoder\'s inference path, whose dropouts are the identity: '
+                          "the result is the eval() one although the model is in train() mode", stacklevel=3)
+        rows = x.transpose(1, 2).contiguous().float()
+        gt = gt.detach().contiguous().float()
+        with torch.no_grad():                                        # the sample is a constant
+            fps_gt = furthest_point_sample(gt, rows.shape[1])
+            y = _take_rows(gt, fps_gt).contiguous()
+        feat = self.encoder(torch.cat((rows, y), dim=0))
+        q_mu, q_std, p_mu, p_std, z, global_feat, dl_rec, dl_g = self._latent_head(*feat.chunk(2), eps)
+        x2, gt2 = torch.cat((rows, rows), dim=0), torch.cat((gt, gt), dim=0)
+        coarse_raw, coarse_high, coarse, fine = self.decoder(global_feat, x2, self.trace)
+        loss1, _ = cd_loss(coarse_raw, gt2)
+        loss2, _ = cd_loss(coarse_high, gt2)
+        loss3, _ = cd_loss(coarse, gt2)
+        loss4, loss4_t = cd_loss(fine, gt2)
+        total = loss1.mean() * 10 + loss2.mean() * 0.5 + loss3.mean() + loss4.mean() * alpha
+        total = total + (dl_rec.mean() + dl_g.mean()) * 20
+        if self.trace is not None:                       # detached: a trace that is kept does not keep the step's graph alive
+            rec = dict(feat=feat, fps_gt=fps_gt, q_mu=q_mu, q_std=q_std, p_mu=p_mu, p_std=p_std, z=z, global_feat=global_feat,
+                       dl_rec=dl_rec, dl_g=dl_g, loss1=loss1, loss2=loss2, loss3=loss3, loss4=loss4,
+                       coarse_raw=coarse_raw, coarse_high=coarse_high, coarse=coarse, fine=fine)
+            self.trace.update({n: t.detach() for n, t in rec.items()})
+        return fine, loss4_t, total
+
+    def _latent_head(self, feat_x, feat_y, eps):
+        """vrcnet.py:578-605 and :622-625 from the two halves of the encoder's output: -> (q_mu, q_std, p_mu, p_std, z,
+        global_feat, dl_rec, dl_g).  The two ReLUs are the reference's in-place ones: relu(feat_x) is what the generator's
+        output is added to."""
+        Normal, kl = torch.distributions.Normal, torch.distributions.kl_divergence
+        B = feat_x.shape[0]
+        feat_x, feat_y = torch.relu(feat_x), torch.relu(feat_y)
+        q_mu, q_std = torch.split(self.posterior_infer2(self.posterior_infer1(feat_x)), self.size_z, dim=1)
+        p_mu, p_std = torch.split(self.prior_infer(feat_y), self.size_z, dim=1)
+        q_std, p_std = F.softplus(q_std), F.softplus(p_std)
+        if eps is None:
+            eps = (torch.randn_like(q_mu), torch.randn_like(p_mu))
+        eps_q, eps_p = (e.detach().to(feat_x.dtype) for e in eps)
+        if tuple(eps_q.shape) != (B, self.size_z) or tuple(eps_p.shape) != (B, self.size_z):
+            raise ValueError(f"VRCNet: eps must be a pair of [{B},{self.size_z}] tensors")
+        z = torch.cat((q_mu + q_std * eps_q, p_mu + p_std * eps_p), dim=0).contiguous()
+        global_feat = torch.cat((feat_x, feat_x), dim=0) + self.generator(z)
+        dl_rec = kl(Normal(torch.zeros_like(p_mu), torch.ones_like(p_std)), Normal(p_mu, p_std))
+        dl_g = kl(Normal(p_mu.detach(), p_std.detach()), Normal(q_mu, q_std))
+        return q_mu, q_std, p_mu, p_std, z, global_feat, dl_rec, dl_g
+
+    def _forward_infer(self, x, gt, prefix, z):
         rows = x.transpose(1, 2).contiguous().float()
         feat = self.encoder(rows)
         o_x = self.posterior_infer2(self.posterior_infer1(feat))

@@ -866,6 +866,44 @@ def edge_pool_backward(g, p_idx, pn_idx, arg, N):
     return gfeat
 
 
+def cd_loss_backward(output, gt, dist1, dist2, idx1, idx2, g_p, g_t, gout=None, workspace=None):
+    """The gradient of calc_cd(output, gt) with respect to output (houv_cd_loss_backward): output[B,M,3],
+    gt[B,N,3], what chamfer_forward(gt, output) gave (dist1[B,N], dist2[B,M], int32 idx1[B,N] rows of output, idx2[B,M] rows of
+    gt) and the upstream gradients g_p[B], g_t[B] of cd_p and cd_t -> gout[B,M,3], every element written: the own term, then the
+    terms of the ground-truth points that chose the row, in ascending order.  Deterministic: no float atomics.  `gout` and the
+    int32 `workspace` (houv_cd_loss_backward_workspace_bytes) are allocated here unless given."""
+    _lib.require_gpu(output, gt, dist1, dist2, idx1, idx2, g_p, g_t, gout, workspace)
+    for t, d, n in ((output, _F32, "output"), (gt, _F32, "gt"), (dist1, _F32, "dist1"), (dist2, _F32, "dist2"), (idx1, _I32, "idx1"),
+                    (idx2, _I32, "idx2"), (g_p, _F32, "g_p"), (g_t, _F32, "g_t")):
+        _want(t, d, f"cd_loss_backward: {n}")
+    if output.dim() != 3 or gt.dim() != 3 or output.shape[2] != 3 or gt.shape[2] != 3 or gt.shape[0] != output.shape[0]:
+        raise _lib.HouvHipError(f"cd_loss_backward: expected output[B,M,3] and gt[B,N,3], got {tuple(output.shape)} and {tuple(gt.shape)}")
+    B, M, _ = output.shape
+    N = gt.shape[1]
+    if (tuple(dist1.shape) != (B, N) or tuple(idx1.shape) != (B, N) or tuple(dist2.shape) != (B, M) or tuple(idx2.shape) != (B, M)
+            or g_p.numel() != B or g_t.numel() != B):
+        raise _lib.HouvHipError(f"cd_loss_backward: expected dist1, idx1 [{B},{N}], dist2, idx2 [{B},{M}] and g_p, g_t [{B}], got "
+                                f"{tuple(dist1.shape)}, {tuple(idx1.shape)}, {tuple(dist2.shape)}, {tuple(idx2.shape)}, "
+                                f"{tuple(g_p.shape)}, {tuple(g_t.shape)}")
+    dev = output.device
+    if gout is None:
+        gout = torch.empty((B, M, 3), dtype=_F32, device=dev)
+    _want(gout, _F32, "cd_loss_backward: gout")
+    if tuple(gout.shape) != (B, M, 3):
+        raise _lib.HouvHipError(f"cd_loss_backward: gout must be [{B},{M},3], got {tuple(gout.shape)}")
+    lib = _lib.load()
+    nbytes = lib.houv_cd_loss_backward_workspace_bytes(B, N, M)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=dev)
+    _want(workspace, _I32, "cd_loss_backward: workspace")
+    with torch.cuda.device(dev):
+        ok = lib.houv_cd_loss_backward(_lib.ptr(output), _lib.ptr(gt), _lib.ptr(dist1), _lib.ptr(dist2), _lib.ptr(idx1), _lib.ptr(idx2),
+                                       _lib.ptr(g_p), _lib.ptr(g_t), B, N, M, _lib.ptr(gout), _lib.ptr(workspace),
+                                       4 * workspace.numel(), _lib.stream_of(output))
+    _lib.check(ok, "houv_cd_loss_backward")
+    return gout
+
+
 def _ef_expand_args(who, proj, idx, W2a, W3, r):
     """(B, N, O, k, ldp, ldw) of ef_expand's operands: proj[B,N,2O+2Or] rows (one row stride), idx[B,N,k] int32, W2a[O r, O] rows
     of any stride (a column slice of conv2's weight), W3[O,O] dense."""

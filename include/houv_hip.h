@@ -720,6 +720,26 @@ int houv_ef_expand_backward(const float* proj, int ldp, const int32_t* idx, cons
                             float* gW2a, float* gW3, float* gb3, void* workspace, long long workspace_bytes, void* stream);
 long long houv_ef_expand_backward_workspace_bytes(int B, int N, int O, int k, int r);
 
+/* The gradient of the completion Chamfer loss calc_cd(output, gt) with respect to the output cloud.
+ * gt[B,N,3], output[B,M,3] and what houv_chamfer_forward(gt, output) gave: dist1[B,N], dist2[B,M], idx1[B,N] (rows of output),
+ * idx2[B,M] (rows of gt).  With the upstream gradients g_p[B] of cd_p = (mean sqrt(dist1) + mean sqrt(dist2)) / 2 and g_t[B] of
+ * cd_t = mean dist1 + mean dist2:
+ *   w1[i] = g_t / N + (g_p / (4 N)) / sqrt(dist1[i]),      w2[j] = g_t / M + (g_p / (4 M)) / sqrt(dist2[j])
+ *   gout[b,j] = 2 w2[j] (out[j] - gt[idx2[j]]), then + 2 w1[i] (out[j] - gt[i]) for every i with idx1[i] == j, i ascending
+ * gout[B,M,3] is WRITTEN, every element: it need not be zeroed.  No float atomics: a list of up to 32 entries is added one entry
+ * after the other; a longer one by 64 lanes (lane l takes entries l, l + 64, ... in order) and a fixed xor butterfly, so the
+ * order of every sum is a function of its list and two calls give the same bits, at any B.  A zero distance is not clamped:
+ * such a row is NaN, as the composition sqrt -> mean -> backward makes it.  An idx1 entry outside 0..M-1 or an idx2 entry outside
+ * 0..N-1 is clamped into that range: nothing outside the clouds is read.  The gradient with respect to gt is not computed.
+ * The workspace holds int32 arrays only: the CSR inverse of idx1 from houv_scatter_points_grad's stable counting sort, offsets
+ * [B,M+1] and order [B,N]; houv_cd_loss_backward_workspace_bytes(B, N, M) bytes (0 for arguments out of range), 16-byte aligned,
+ * caller-allocated; a smaller, NULL or misaligned workspace is refused.  Refused by name: N <= 0, M <= 0, B < 0, a NULL pointer;
+ * B = 0 launches nothing. */
+int houv_cd_loss_backward(const float* output, const float* gt, const float* dist1, const float* dist2, const int32_t* idx1,
+                          const int32_t* idx2, const float* g_p, const float* g_t, int B, int N, int M, float* gout,
+                          void* workspace, long long workspace_bytes, void* stream);
+long long houv_cd_loss_backward_workspace_bytes(int B, int N, int M);
+
 /* Pose only (HOUV.forward, houv.py:94-103): params fp32 [n,8] -> R[n,9], T[n,3]; if src != NULL
  * also moved[n,N,3] = src[n,N,3] @ R^T + T. */
 int houv_pose_forward(const float* params, int n, int angle_base, int trans_mode,
