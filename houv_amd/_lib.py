@@ -41,6 +41,7 @@ _SIGNATURES = {
     "houv_solve_stage_pruned": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int,
                                                _int, _int, _int, _dbl, _dbl, _dbl, _dbl, _flt, _c_f, _c_f, _c_f, _c_f,
                                                _c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f]),
+    "houv_solve_seed": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _c_f, _int, _c_f]),
     "houv_solve_variant": (ctypes.c_int, [_int, _int, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int)]),
     "houv_solve_lds_bytes": (ctypes.c_longlong, [_int, _int, _int]),

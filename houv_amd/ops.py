@@ -169,6 +169,29 @@ def solve_workspace(n_hypotheses, N, M, device):
     return torch.empty((int(n_hypotheses), 16, stride), dtype=torch.int16, device=device)
 
 
+def solve_seed(src, tgt, state, K, angle_base, trans_mode, use_views, nn_ws):
+    """houv_solve_seed: first-guess neighbour records for the poses of ``state`` [P*K,24] fp64 written into ``nn_ws``
+    (solve_workspace), so that the next solve_iterate on them may start with ``ws_valid=True``: its first iteration then runs the
+    pruned search instead of the brute-force sweep, with the same results.  Clouds of 257..4096 points.  Returns 1."""
+    _lib.require_gpu(src, tgt, state, nn_ws)
+    _want(src, _F32, "src"); _want(tgt, _F32, "tgt"); _want(state, _F64, "state")
+    P, N, _ = src.shape
+    M = tgt.shape[1]
+    if tgt.shape[0] != P or src.shape[2] != 3 or tgt.shape[2] != 3:
+        raise _lib.HouvHipError("solve_seed: expected src[P,N,3], tgt[P,M,3]")
+    n = P * int(K)
+    if tuple(state.shape) != (n, 24):
+        raise _lib.HouvHipError(f"solve_seed: state must be [{n},24], got {tuple(state.shape)}")
+    if nn_ws is None or nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16):
+        raise _lib.HouvHipError("solve_seed: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
+    with torch.cuda.device(src.device):
+        ok = _lib.load().houv_solve_seed(_lib.ptr(src), _lib.ptr(tgt), P, N, M, int(K), _lib.ptr(state), int(angle_base),
+                                         int(trans_mode), int(bool(use_views)), _lib.ptr(nn_ws), nn_ws.shape[2],
+                                         _lib.stream_of(src))
+    _lib.check(ok, "houv_solve_seed")
+    return 1
+
+
 def solve_sched_workspace(n_hypotheses, device):
     """Scheduling workspace of houv_solve_stage[_pruned] for n hypotheses: int32 [4 + n] (ticket counter, status word, two spares,
     done[h]).  One per stage in flight; the call zeroes it.  Word 1 is the status: non-zero after the launch = the stage failed."""

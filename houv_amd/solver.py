@@ -17,6 +17,8 @@ ITERS_PER_LAUNCH = 50        # iterations per item of a stage (houv_solve_stage:
 
 # bench.py sets this to a list to collect (start_event, end_event, hypotheses, iterations, N, M, use_views, pruned, first) per
 # houv_solve_iterate[_pruned|_large] / houv_solve_stage[_pruned] launch: HIP events recorded on the stream the kernel is launched on.
+# `first` = the stage's first launch (tests/test_gpu_solve_stage.py pins it); the events of a seeded stage's first launch span its
+# houv_solve_seed launch too, and no entry of its own is made for that.
 LAUNCH_LOG = None
 
 # Status words of the houv_solve_stage launches not yet looked at: (sched_ws, event recorded behind the launch).  Non-zero = a
@@ -84,6 +86,13 @@ PRUNED = os.environ.get("HOUV_SOLVER", "pruned").strip().lower() != "brute"
 PRUNED_MAX_POINTS = 4096     # the fused kernel's limit; above 2048 points a visit-mask bit covers a 64-point super-tile
 PRUNED_MIN_POINTS = 257      # up to 256 points (8 sub-tiles, one point per lane) the library itself runs the brute-force kernel
                              # (houv_solve_variant reports prune mode 0); from 257 on the search pays (profiles/r03_sizes.txt)
+
+
+# A stage of the pruned kernel starts from first-guess neighbour records (houv_solve_seed, csrc/solve_seed.hip) instead of an empty
+# workspace: its first iteration then runs the pruned search too, not the brute-force sweep over all sub-tiles.  Any in-range
+# record at a finite distance is an attained bound and iteration 0 rescans every term, so the results are the same bits either way
+# (tests/test_gpu_solve_seed.py); ``houv_amd.solver.SEED_FIRST = False`` or HOUV_SOLVE_SEED=0 gives the unseeded stage for A/B runs.
+SEED_FIRST = os.environ.get("HOUV_SOLVE_SEED", "1").strip().lower() not in ("0", "false", "off", "no")
 
 
 def uses_pruned(N, M, pruned=None):
@@ -431,6 +440,11 @@ def run_stage(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views
         leaf = sort_leaf(N, tgt.shape[1])
         src, tgt = spatial_sort(src, leaf), spatial_sort(tgt, leaf)
         nn_ws = ops.solve_workspace(n, N, tgt.shape[1], dev)
+    seeded = nn_ws is not None and SEED_FIRST and pruned != "verify"
+
+    def seed():
+        # same stream, in front of the stage's first launch (inside its LAUNCH_LOG events: the seed is part of the stage's cost)
+        ops.solve_seed(src, tgt, state, K, angle_base, trans_mode, use_views, nn_ws)
     done, out = 0, None
     last_params = None
     if not iters_per_launch and not want_last_params:
@@ -440,10 +454,12 @@ def run_stage(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views
             ev0 = torch.cuda.Event(enable_timing=True)
             ev1 = torch.cuda.Event(enable_timing=True)
             ev0.record(torch.cuda.current_stream(dev))
+        if seeded:
+            seed()
         out = ops.solve_iterate(src, tgt, state, K, steps_done=0, n_iters=n_iters, angle_base=angle_base,
                                 trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
                                 k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad, want_cd=want_cd, nn_ws=nn_ws,
-                                ws_valid="verify" if pruned == "verify" else False, chunk_iters=step, sched_ws=sched_ws)
+                                ws_valid="verify" if pruned == "verify" else seeded, chunk_iters=step, sched_ws=sched_ws)
         if LAUNCH_LOG is not None:
             ev1.record(torch.cuda.current_stream(dev))
             LAUNCH_LOG.append((ev0, ev1, n, n_iters, N, tgt.shape[1], bool(use_views), nn_ws is not None, True))
@@ -466,11 +482,13 @@ def run_stage(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views
             ev0 = torch.cuda.Event(enable_timing=True)
             ev1 = torch.cuda.Event(enable_timing=True)
             ev0.record(torch.cuda.current_stream(dev))
+        if seeded and done == 0:
+            seed()
         out = ops.solve_iterate(src, tgt, state, K, steps_done=done, n_iters=it, angle_base=angle_base,
                                 trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
                                 k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad and last,
                                 want_cd=want_cd and last, nn_ws=nn_ws,
-                                ws_valid="verify" if pruned == "verify" else done > 0)
+                                ws_valid="verify" if pruned == "verify" else (done > 0 or seeded))
         if LAUNCH_LOG is not None:
             ev1.record(torch.cuda.current_stream(dev))
             LAUNCH_LOG.append((ev0, ev1, n, it, N, tgt.shape[1], bool(use_views), nn_ws is not None, done == 0))

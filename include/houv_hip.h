@@ -160,6 +160,25 @@ int houv_solve_stage_pruned(const float* src, const float* tgt, int P, int N, in
                             int16_t* nn_ws, int ws_valid, int ws_stride,
                             int chunk_iters, int32_t* sched_ws, void* stream);
 
+/* First-guess neighbour records for the pruned solve: after this call a stage may start with ws_valid = 1, so that its first
+ * iteration runs the pruned search instead of the brute-force sweep.  Any in-range record whose reference lies at a finite
+ * distance is an attained bound, so the solve's results do not depend on the guess -- only the length of the first visit lists does.
+ * One workgroup per hypothesis: the pose of state[h, 0:8] (fp32, as the solve's prologue forms it) moves the source cloud; both
+ * clouds get the boxes of their 32-point runs (a last, partly filled run from its existing points); then, for both directions,
+ * every query and every metric in use (metric 0 alone without views) takes the run whose box is nearest to the query in that
+ * metric's projection (the query clamped into the box; the lowest run wins ties), and of that run the point nearest in that metric
+ * (the lowest index wins ties; strict < from +inf, so a NaN distance never wins).  A query whose chosen run holds no reference at
+ * a finite distance takes the first reference of the whole cloud at a finite distance, and 0 when there is none (a NaN query).
+ * The records go where the solve reads them: per hypothesis 4 x int16 per query at byte q * 8, metric m at int16 m; direction B
+ * (queries = target points, indices into the source order) from byte 0, direction A (queries = moved points, indices into the
+ * target) from byte ws_stride * 8.  Rows 8..15 of the workspace, and the int16 of metrics not in use, are left as they are.
+ * Every index written is in [0, count) of the cloud it points into.
+ * Limits: 257 <= max(N, M) <= 4096 (the sizes the pruned kernels serve); nn_ws non-null and 16-byte aligned; ws_stride >= max(N, M)
+ * and a multiple of 8; angle_base 0..3, trans_mode 0..1.  Returns 1 at once when P == 0; 0 with houv_last_error() set, launching
+ * nothing, when a check fails.  No counterpart in the reference. */
+int houv_solve_seed(const float* src, const float* tgt, int P, int N, int M, int K, const double* state,
+                    int angle_base, int trans_mode, int use_views, int16_t* nn_ws, int ws_stride, void* stream);
+
 /* Fused loop for LARGE clouds (what houv_amd.solver runs for 4097..16384 points): the same arguments, outputs and arithmetic
  * contract as houv_solve_iterate, for clouds that do not fit in LDS.  Neither cloud is resident: every workgroup (1024 threads,
  * one hypothesis) holds 4096 query points at a time in registers and streams the other cloud through a double-buffered LDS
