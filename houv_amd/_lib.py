@@ -18,6 +18,14 @@ _int = ctypes.c_int
 _dbl = ctypes.c_double
 _flt = ctypes.c_float
 
+# the fused solve's entries: 26 common arguments (clouds, sizes, state, iteration window, switches, top-k sizes, Adam constants,
+# loss scale, six outputs), then the pruned search's workspace (nn_ws, ws_valid, stride) and / or the stage's schedule
+# (chunk_iters, sched_ws) as the entry has them, then the stream
+_SOLVE_COMMON = [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int, _int, _int, _int, _dbl, _dbl, _dbl, _dbl,
+                 _flt, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]
+_SOLVE_WS = [_c_f, _int, _int]
+_SOLVE_SCHED = [_int, _c_f]
+
 _SIGNATURES = {
     "houv_abi_version": (ctypes.c_int, []),
     "houv_last_error": (ctypes.c_char_p, []),
@@ -26,21 +34,11 @@ _SIGNATURES = {
     "houv_chamfer_forward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_chamfer_backward": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "houv_kabsch": (ctypes.c_int, [_c_f, _c_f, _c_f, _int, _int, _c_f, _c_f, _c_f]),
-    "houv_solve_iterate": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int, _int,
-                                          _int, _int, _dbl, _dbl, _dbl, _dbl, _flt, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
-                                          _c_f]),
-    "houv_solve_iterate_large": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int, _int,
-                                                _int, _int, _dbl, _dbl, _dbl, _dbl, _flt, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
-                                                _c_f]),
-    "houv_solve_iterate_pruned": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int,
-                                                 _int, _int, _int, _dbl, _dbl, _dbl, _dbl, _flt, _c_f, _c_f, _c_f, _c_f,
-                                                 _c_f, _c_f, _c_f, _int, _int, _c_f]),
-    "houv_solve_stage": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int, _int,
-                                        _int, _int, _dbl, _dbl, _dbl, _dbl, _flt, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
-                                        _int, _c_f, _c_f]),
-    "houv_solve_stage_pruned": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _int, _int,
-                                               _int, _int, _int, _dbl, _dbl, _dbl, _dbl, _flt, _c_f, _c_f, _c_f, _c_f,
-                                               _c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f]),
+    "houv_solve_iterate": (ctypes.c_int, _SOLVE_COMMON + [_c_f]),
+    "houv_solve_iterate_large": (ctypes.c_int, _SOLVE_COMMON + [_c_f]),
+    "houv_solve_iterate_pruned": (ctypes.c_int, _SOLVE_COMMON + _SOLVE_WS + [_c_f]),
+    "houv_solve_stage": (ctypes.c_int, _SOLVE_COMMON + _SOLVE_SCHED + [_c_f]),
+    "houv_solve_stage_pruned": (ctypes.c_int, _SOLVE_COMMON + _SOLVE_WS + _SOLVE_SCHED + [_c_f]),
     "houv_solve_seed": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _c_f, _int, _int, _int, _c_f, _int, _c_f]),
     "houv_solve_variant": (ctypes.c_int, [_int, _int, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_int)]),

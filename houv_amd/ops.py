@@ -93,6 +93,13 @@ def pose_forward(params, angle_base, trans_mode=0, src=None):
     return (R, T) if src is None else (R, T, moved)
 
 
+def _want_nn_ws(nn_ws, n, who):
+    """The pruned search's workspace for n hypotheses (solve_workspace)."""
+    if (nn_ws is None or nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16)
+            or not nn_ws.is_contiguous()):
+        raise _lib.HouvHipError(f"{who}: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
+
+
 def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans_mode, use_views, f64_params, k_full,
                       k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad=None,
                       out_cd=None, nn_ws=None, ws_valid=0, large=False, chunk_iters=None, sched_ws=None):
@@ -120,34 +127,22 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
               int(angle_base), int(trans_mode), int(bool(use_views)), int(bool(f64_params)), int(k_full), int(k_view),
               float(lr), float(beta1), float(beta2), float(eps), float(loss_scale), _lib.ptr(out_score),
               _lib.ptr(out_loss), _lib.ptr(out_R), _lib.ptr(out_T), _lib.ptr(out_grad), _lib.ptr(out_cd))
+    stage = sched_ws is not None
     if large and nn_ws is not None:
         raise _lib.HouvHipError("solve_iterate: the large-cloud kernel is a brute-force sweep and takes no workspace")
-    stage = sched_ws is not None
+    if large and stage:
+        raise _lib.HouvHipError("solve_iterate: the large-cloud kernel has no stage form")
+    name = ("houv_solve_stage" if stage else "houv_solve_iterate") + ("_large" if large else "_pruned" if nn_ws is not None else "")
+    if stage and (sched_ws.dtype != torch.int32 or sched_ws.numel() < 4 + n):
+        raise _lib.HouvHipError(f"solve_iterate: sched_ws must hold {4 + n} int32 (ops.solve_sched_workspace)")
+    if nn_ws is not None:   # exact pruned search: nn_ws int16 [P*K, 16, stride] (solve_workspace) persists between chunked launches
+        _want_nn_ws(nn_ws, n, "solve_iterate")
+        common += (_lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2])
     if stage:
-        if large:
-            raise _lib.HouvHipError("solve_iterate: the large-cloud kernel has no stage form")
-        if sched_ws.dtype != torch.int32 or sched_ws.numel() < 4 + n:
-            raise _lib.HouvHipError(f"solve_iterate: sched_ws must hold {4 + n} int32 (ops.solve_sched_workspace)")
-        sched = (int(chunk_iters), _lib.ptr(sched_ws))
+        common += (int(chunk_iters), _lib.ptr(sched_ws))
     with torch.cuda.device(src.device):
-        if large:
-            ok = _lib.load().houv_solve_iterate_large(*common, _lib.stream_of(src))
-        elif stage and nn_ws is None:
-            ok = _lib.load().houv_solve_stage(*common, *sched, _lib.stream_of(src))
-        elif stage:
-            if nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16) or not nn_ws.is_contiguous():
-                raise _lib.HouvHipError("solve_iterate: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
-            ok = _lib.load().houv_solve_stage_pruned(*common, _lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2], *sched,
-                                                     _lib.stream_of(src))
-        elif nn_ws is None:
-            ok = _lib.load().houv_solve_iterate(*common, _lib.stream_of(src))
-        else:   # exact pruned search: nn_ws int16 [P*K, 16, stride] (solve_workspace) persists between chunked launches
-            if nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16) or not nn_ws.is_contiguous():
-                raise _lib.HouvHipError("solve_iterate: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
-            ok = _lib.load().houv_solve_iterate_pruned(*common, _lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2],
-                                                       _lib.stream_of(src))
-    _lib.check(ok, ("houv_solve_stage" if stage else "houv_solve_iterate") +
-               ("_large" if large else "_pruned" if nn_ws is not None else ""))
+        ok = getattr(_lib.load(), name)(*common, _lib.stream_of(src))
+    _lib.check(ok, name)
     return 1
 
 
@@ -182,8 +177,7 @@ def solve_seed(src, tgt, state, K, angle_base, trans_mode, use_views, nn_ws):
     n = P * int(K)
     if tuple(state.shape) != (n, 24):
         raise _lib.HouvHipError(f"solve_seed: state must be [{n},24], got {tuple(state.shape)}")
-    if nn_ws is None or nn_ws.dtype != torch.int16 or nn_ws.dim() != 3 or tuple(nn_ws.shape[:2]) != (n, 16):
-        raise _lib.HouvHipError("solve_seed: nn_ws must be a contiguous int16 [P*K,16,stride] tensor (ops.solve_workspace)")
+    _want_nn_ws(nn_ws, n, "solve_seed")
     with torch.cuda.device(src.device):
         ok = _lib.load().houv_solve_seed(_lib.ptr(src), _lib.ptr(tgt), P, N, M, int(K), _lib.ptr(state), int(angle_base),
                                          int(trans_mode), int(bool(use_views)), _lib.ptr(nn_ws), nn_ws.shape[2],

@@ -8,7 +8,7 @@ import weakref
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 RETRY_THRESHOLD = 0.030      # houv.py:156, train_utils.py:494 (strict >)
 ITERS_PER_LAUNCH = 50        # iterations per item of a stage (houv_solve_stage: one launch per stage, whose persistent grid
@@ -17,8 +17,9 @@ ITERS_PER_LAUNCH = 50        # iterations per item of a stage (houv_solve_stage:
 
 # bench.py sets this to a list to collect (start_event, end_event, hypotheses, iterations, N, M, use_views, pruned, first) per
 # houv_solve_iterate[_pruned|_large] / houv_solve_stage[_pruned] launch: HIP events recorded on the stream the kernel is launched on.
-# `first` = the stage's first launch (tests/test_gpu_solve_stage.py pins it); the events of a seeded stage's first launch span its
-# houv_solve_seed launch too, and no entry of its own is made for that.
+# run_stage's launch loop is the one place that makes an entry.  `first` = the first launch of its block of pairs, steps_done == 0
+# (tests/test_gpu_solve_stage.py pins it); the events of a seeded stage's first launch span its houv_solve_seed launch too, and no
+# entry of its own is made for that.
 LAUNCH_LOG = None
 
 # Status words of the houv_solve_stage launches not yet looked at: (sched_ws, event recorded behind the launch).  Non-zero = a
@@ -292,56 +293,6 @@ def large_launch_plan(P, K, N, M, n_cu, budget_s=None):
     return pairs, max(1, min(ITERS_PER_LAUNCH, rounds // waves))
 
 
-def _run_stage_large(src, tgt, p, K, n_iters, *, angle_base, trans_mode, use_views, f64_params, lr, iters_per_launch,
-                     want_grad, want_cd, alpha, want_last_params):
-    """run_stage for clouds of 4097..16384 points: launches of houv_solve_iterate_large, split along iterations and pairs as
-    large_launch_plan says (bit-neutral: each hypothesis is independent and its state round-trips through HBM exactly)."""
-    from . import _lib
-    _lib.require_gpu(src, tgt)
-    P, N, _ = src.shape
-    M = tgt.shape[1]
-    dev = src.device
-    n = P * K
-    state = torch.zeros((n, 24), dtype=torch.float64, device=dev)
-    state[:, :8] = p.to(dev)
-    k_full, k_view = int(N * alpha), int(N * 1)
-    pairs, step = large_launch_plan(P, K, N, M, torch.cuda.get_device_properties(dev).multi_processor_count)
-    if iters_per_launch:
-        step = min(step, iters_per_launch)
-    last_params = torch.empty((n, 8), dtype=torch.float64, device=dev) if want_last_params else None
-    outs = []
-    for p0 in range(0, P, pairs):
-        p1 = min(P, p0 + pairs)
-        rows = slice(p0 * K, p1 * K)
-        s_src, s_tgt, s_state = src[p0:p1], tgt[p0:p1], state[rows]
-        done, out = 0, None
-        while done < n_iters:
-            it = min(step, n_iters - done)
-            if want_last_params:
-                if done == n_iters - 1:
-                    last_params[rows] = s_state[:, :8]
-                else:
-                    it = min(it, n_iters - 1 - done)
-            last = done + it == n_iters
-            if LAUNCH_LOG is not None:
-                ev0 = torch.cuda.Event(enable_timing=True)
-                ev1 = torch.cuda.Event(enable_timing=True)
-                ev0.record(torch.cuda.current_stream(dev))
-            out = ops.solve_iterate(s_src, s_tgt, s_state, K, steps_done=done, n_iters=it, angle_base=angle_base,
-                                    trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
-                                    k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad and last,
-                                    want_cd=want_cd and last, large=True)
-            if LAUNCH_LOG is not None:
-                ev1.record(torch.cuda.current_stream(dev))
-                LAUNCH_LOG.append((ev0, ev1, (p1 - p0) * K, it, N, M, bool(use_views), False, done == 0))
-            done += it
-        outs.append(out)
-    out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
-    if want_last_params:
-        out["last_params"] = last_params
-    return out, state
-
-
 def _run_stage_unfused(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views, f64_params, lr, want_grad,
                        want_cd, alpha):
     """Clouds too large for the fused kernel's LDS: the loop in the reference's own shape -- differentiable forward
@@ -398,101 +349,108 @@ def _run_stage_unfused(src, tgt, params, K, n_iters, *, angle_base, trans_mode, 
     return out, state
 
 
+def _cuts(n_iters, step, want_last_params):
+    """The launches ``n_iters`` iterations are cut into: (steps_done, iterations, is_last), at most ``step`` iterations each; with
+    ``want_last_params`` the last launch is exactly one iteration (the parameters it reads are copied out in front of it)."""
+    done = 0
+    while done < n_iters:
+        it = min(step, n_iters - done)
+        if want_last_params and done < n_iters - 1:
+            it = min(it, n_iters - 1 - done)
+        yield done, it, done + it == n_iters
+        done += it
+
+
 def run_stage(src, tgt, params, K, n_iters, *, angle_base, trans_mode, use_views, f64_params, lr,
               iters_per_launch=None, want_grad=False, want_cd=False, alpha=0.5, pruned=None, want_last_params=False):
     """Run ``n_iters`` optimisation iterations for P*K hypotheses.  params: float64 [P*K,8] (numpy or tensor).
     Returns (out dict of the last forward, state tensor [P*K,24] fp64 after n_iters Adam steps).
     ``want_last_params``: also return, as out["last_params"] (fp64 [P*K,8]), the parameters the LAST forward read, i.e.
-    before the final Adam step (the last launch is then exactly one iteration; chunking is bit-neutral)."""
+    before the final Adam step (the last launch is then exactly one iteration; chunking is bit-neutral).
+    One loop over (block of pairs, cut of iterations) makes every launch; the three forms differ in the plan they hand it:
+    the one-launch stage (one block, one cut, houv_solve_stage[_pruned] runs it as items of ITERS_PER_LAUNCH iterations), the
+    chunked form (one block; ``iters_per_launch`` or ``want_last_params``) and the large form (clouds of 4097..16384 points:
+    houv_solve_iterate_large, split along iterations and pairs as large_launch_plan says -- bit-neutral, each hypothesis is
+    independent and its state round-trips through HBM exactly)."""
     if n_iters < 1:
         raise ValueError("num_epochs must be >= 1 (the reference reads the last iteration's outputs)")
     src = src.contiguous().float()
     tgt = tgt.contiguous().float()
     P, N, _ = src.shape
-    if use_views and tgt.shape[1] != N:
+    M = tgt.shape[1]
+    if use_views and M != N:
         # loss_view multiplies the target by a mask shaped like the moved cloud (model_utils_completion.py:158-163):
         # the reference raises on N != M whenever the view terms are on.
-        raise RuntimeError(f"The size of tensor a ({tgt.shape[1]}) must match the size of tensor b ({N}) at "
+        raise RuntimeError(f"The size of tensor a ({M}) must match the size of tensor b ({N}) at "
                            "non-singleton dimension 1")
     dev = src.device
     n = P * K
     p = torch.as_tensor(params, dtype=torch.float64)
     if tuple(p.shape) != (n, 8):
         raise ValueError(f"params must be [{n},8]")
-    if uses_large(N, tgt.shape[1]):
-        return _run_stage_large(src, tgt, p, K, n_iters, angle_base=angle_base, trans_mode=trans_mode, use_views=use_views,
-                                f64_params=f64_params, lr=lr, iters_per_launch=iters_per_launch, want_grad=want_grad,
-                                want_cd=want_cd, alpha=alpha, want_last_params=want_last_params)
-    if max(N, tgt.shape[1]) > FUSED_MAX_POINTS:
-        from . import _lib
+    large = uses_large(N, M)
+    if large or max(N, M) > FUSED_MAX_POINTS:
         _lib.require_gpu(src, tgt)
-        return _run_stage_unfused(src, tgt, p, K, n_iters, angle_base=angle_base, trans_mode=trans_mode,
-                                  use_views=use_views, f64_params=f64_params, lr=lr, want_grad=want_grad,
-                                  want_cd=want_cd, alpha=alpha)
+        if not large:
+            return _run_stage_unfused(src, tgt, p, K, n_iters, angle_base=angle_base, trans_mode=trans_mode,
+                                      use_views=use_views, f64_params=f64_params, lr=lr, want_grad=want_grad,
+                                      want_cd=want_cd, alpha=alpha)
     state = torch.zeros((n, 24), dtype=torch.float64, device=dev)
     state[:, :8] = p.to(dev)
-    k_full = int(N * alpha)            # model_utils_completion.py:85-86 with percent = alpha
-    k_view = int(N * 1)
-    step = iters_per_launch or ITERS_PER_LAUNCH
-    pruned = PRUNED if pruned is None else pruned
-    nn_ws = None
-    if uses_pruned(N, tgt.shape[1], pruned):
-        leaf = sort_leaf(N, tgt.shape[1])
-        src, tgt = spatial_sort(src, leaf), spatial_sort(tgt, leaf)
-        nn_ws = ops.solve_workspace(n, N, tgt.shape[1], dev)
-    seeded = nn_ws is not None and SEED_FIRST and pruned != "verify"
+    kernel_kw = dict(angle_base=angle_base, trans_mode=trans_mode, use_views=use_views, f64_params=f64_params,
+                     k_full=int(N * alpha),        # model_utils_completion.py:85-86 with percent = alpha
+                     k_view=int(N * 1), lr=lr, loss_scale=1.0 / n, large=large)
 
-    def seed():
-        # same stream, in front of the stage's first launch (inside its LAUNCH_LOG events: the seed is part of the stage's cost)
-        ops.solve_seed(src, tgt, state, K, angle_base, trans_mode, use_views, nn_ws)
-    done, out = 0, None
-    last_params = None
-    if not iters_per_launch and not want_last_params:
-        # the whole stage in ONE launch: items of ITERS_PER_LAUNCH iterations, bit for bit the launches of the loop below
-        sched_ws = ops.solve_sched_workspace(n, dev)
-        if LAUNCH_LOG is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record(torch.cuda.current_stream(dev))
-        if seeded:
-            seed()
-        out = ops.solve_iterate(src, tgt, state, K, steps_done=0, n_iters=n_iters, angle_base=angle_base,
-                                trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
-                                k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad, want_cd=want_cd, nn_ws=nn_ws,
-                                ws_valid="verify" if pruned == "verify" else seeded, chunk_iters=step, sched_ws=sched_ws)
-        if LAUNCH_LOG is not None:
-            ev1.record(torch.cuda.current_stream(dev))
-            LAUNCH_LOG.append((ev0, ev1, n, n_iters, N, tgt.shape[1], bool(use_views), nn_ws is not None, True))
-        if src.is_cuda:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            if len(_STAGE_STATUS) >= 64:
-                check_stage_status(wait=True)
-            _STAGE_STATUS.append((sched_ws, ev))
-        return out, state
-    while done < n_iters:
-        it = min(step, n_iters - done)
-        if want_last_params:
-            if done == n_iters - 1:
-                last_params = state[:, :8].clone()
-            else:
-                it = min(it, n_iters - 1 - done)
-        last = done + it == n_iters
-        if LAUNCH_LOG is not None:
-            ev0 = torch.cuda.Event(enable_timing=True)
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record(torch.cuda.current_stream(dev))
-        if seeded and done == 0:
-            seed()
-        out = ops.solve_iterate(src, tgt, state, K, steps_done=done, n_iters=it, angle_base=angle_base,
-                                trans_mode=trans_mode, use_views=use_views, f64_params=f64_params, k_full=k_full,
-                                k_view=k_view, lr=lr, loss_scale=1.0 / n, want_grad=want_grad and last,
-                                want_cd=want_cd and last, nn_ws=nn_ws,
-                                ws_valid="verify" if pruned == "verify" else (done > 0 or seeded))
-        if LAUNCH_LOG is not None:
-            ev1.record(torch.cuda.current_stream(dev))
-            LAUNCH_LOG.append((ev0, ev1, n, it, N, tgt.shape[1], bool(use_views), nn_ws is not None, done == 0))
-        done += it
+    # the plan: pairs per block, iterations per cut, and whether the stage is ONE houv_solve_stage launch
+    pairs, step, stage = P, iters_per_launch or ITERS_PER_LAUNCH, False
+    nn_ws, seeded, verify = None, False, False
+    if large:
+        pairs, step = large_launch_plan(P, K, N, M, torch.cuda.get_device_properties(dev).multi_processor_count)
+        if iters_per_launch:
+            step = min(step, iters_per_launch)
+    else:
+        pruned = PRUNED if pruned is None else pruned
+        verify = pruned == "verify"
+        if uses_pruned(N, M, pruned):
+            leaf = sort_leaf(N, M)
+            src, tgt = spatial_sort(src, leaf), spatial_sort(tgt, leaf)
+            nn_ws = ops.solve_workspace(n, N, M, dev)
+            seeded = SEED_FIRST and not verify
+        stage = not iters_per_launch and not want_last_params
+    if stage:
+        # items of ITERS_PER_LAUNCH iterations, bit for bit the launches of the chunked form
+        kernel_kw.update(chunk_iters=step, sched_ws=ops.solve_sched_workspace(n, dev))
+        step = n_iters
+    last_params = torch.empty((n, 8), dtype=torch.float64, device=dev) if want_last_params else None
+
+    outs = []
+    for p0 in range(0, P, pairs):
+        p1 = min(P, p0 + pairs)
+        rows = slice(p0 * K, p1 * K)
+        b_src, b_tgt, b_state, b_ws = src[p0:p1], tgt[p0:p1], state[rows], None if nn_ws is None else nn_ws[rows]
+        for done, it, last in _cuts(n_iters, step, want_last_params):
+            if want_last_params and last:
+                last_params[rows] = b_state[:, :8]
+            if LAUNCH_LOG is not None:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record(torch.cuda.current_stream(dev))
+            if seeded and done == 0:
+                # same stream, in front of the stage's first launch and inside its events: the seed is part of the stage's cost
+                ops.solve_seed(b_src, b_tgt, b_state, K, angle_base, trans_mode, use_views, b_ws)
+            out = ops.solve_iterate(b_src, b_tgt, b_state, K, steps_done=done, n_iters=it, want_grad=want_grad and last,
+                                    want_cd=want_cd and last, nn_ws=b_ws,
+                                    ws_valid="verify" if verify else b_ws is not None and (done > 0 or seeded), **kernel_kw)
+            if LAUNCH_LOG is not None:
+                ev1.record(torch.cuda.current_stream(dev))
+                LAUNCH_LOG.append((ev0, ev1, (p1 - p0) * K, it, N, M, bool(use_views), nn_ws is not None, done == 0))
+        outs.append(out)
+    if stage and src.is_cuda:
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        if len(_STAGE_STATUS) >= 64:
+            check_stage_status(wait=True)
+        _STAGE_STATUS.append((kernel_kw["sched_ws"], ev))
+    out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
     if want_last_params:
         out["last_params"] = last_params
     return out, state

@@ -223,3 +223,30 @@ def test_run_stage_makes_one_stage_call_and_keeps_its_results():
     assert torch.equal(st, st_ref)
     for key in KEYS:
         assert torch.equal(got[key], ref[key]), key
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,K,N", [(2, 26, 300), (1, 26, 4097)], ids=["300pt_pruned", "4097pt_large"])
+def test_run_stage_cuts_with_last_params(P, K, N):
+    """solver.run_stage(n_iters=5, iters_per_launch=2, want_last_params=True) -- launches of 2, 2, then 1 and 1 iterations: the cut
+    rule of every form -- returns the outputs and state of the plain 5-iteration stage, and as last_params the parameters a
+    4-iteration stage ends on.  Pruned kernel (seeded) and large kernel; every comparison is on bits."""
+    from houv_amd import solver, synthetic
+    assert torch.cuda.is_available(), "gpu tests need an MI355X"
+    dev = torch.device("cuda:0")
+    assert solver.uses_pruned(N, N) == (N == 300) and solver.uses_large(N, N) == (N == 4097)
+    src, tgt, _ = synthetic.make_pairs(P, N, seed=77)
+    src, tgt = src.to(dev), tgt.to(dev)
+    p0 = torch.as_tensor(solver.houv_init_params(P * K), dtype=torch.float64)
+    kw = dict(angle_base=0, trans_mode=0, use_views=True, f64_params=False, lr=0.01, want_grad=True, want_cd=True)
+    got, st = solver.run_stage(src, tgt, p0, K, 5, iters_per_launch=2, want_last_params=True, **kw)
+    ref, st_ref = solver.run_stage(src, tgt, p0, K, 5, **kw)
+    _, st_4 = solver.run_stage(src, tgt, p0, K, 4, **kw)
+    solver.check_stage_status(wait=True)
+    assert set(got) == set(KEYS) | {"last_params"} and set(ref) == set(KEYS)
+    assert got["last_params"].dtype == torch.float64 and torch.equal(got["last_params"], st_4[:, :8])
+    assert not torch.equal(got["last_params"], st[:, :8])        # the last Adam step did move the parameters
+    assert torch.equal(st, st_ref), "state"
+    for key in KEYS:
+        assert torch.equal(got[key], ref[key]), key
+    assert torch.isfinite(ref["loss"]).all()
