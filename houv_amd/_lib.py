@@ -70,6 +70,15 @@ _SIGNATURES = {
     "houv_rri_features": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _c_f, _c_f]),
     "houv_gmm_params": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f]),
     "houv_gmm_register": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_f, _int, _int, _c_f, _c_f]),
+    "houv_gmm_params_backward": (ctypes.c_int, [_c_f] * 8 + [_int, _int, _int, _c_f, _c_f]),
+    "houv_gmm_register_backward": (ctypes.c_int, [_c_f] * 5 + [_int, _int] + [_c_f] * 5),
+    "houv_bn_rows_workspace_bytes": (ctypes.c_longlong, [ctypes.c_longlong, _int, _int]),
+    "houv_bn_rows_stats": (ctypes.c_int, [_c_f, ctypes.c_longlong, _int, ctypes.c_longlong, _c_f, _c_f, _c_f, ctypes.c_longlong, _c_f]),
+    "houv_bn_relu_rows": (ctypes.c_int, [_c_f, ctypes.c_longlong, _int, ctypes.c_longlong, _c_f, _c_f, _c_f, _c_f, _flt, _int, _int,
+                                         _c_f, ctypes.c_longlong, _c_f, _c_f, _c_f, ctypes.c_longlong, _c_f]),
+    "houv_bn_relu_rows_backward": (ctypes.c_int, [_c_f, ctypes.c_longlong, _c_f, ctypes.c_longlong, _int, ctypes.c_longlong, _c_f, _c_f,
+                                                  _c_f, _c_f, _flt, _int, _c_f, ctypes.c_longlong, _c_f, _c_f, _c_f, ctypes.c_longlong,
+                                                  _c_f]),
     "houv_idam_simmat": (ctypes.c_int, [_c_f] * 4 + [_int] * 4 + [_c_f] * 15),
     "houv_edge_diff": (ctypes.c_int, [_c_f, _c_f, _int, _int, _int, _int, _int, _int, _c_f, _c_f]),
     "houv_mlp2_max": (ctypes.c_int, [_c_f, _int, _int, _int, _c_f, _int, _c_f, ctypes.c_longlong, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),

@@ -227,6 +227,185 @@ __global__ __launch_bounds__(kRegBlock) void gmm_register_kernel(const float* __
   o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Backward of gmm_params with the softmax's folded in: one point per group of J lanes, one pass, nothing of size [B,N,J,3]
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kGmmBwdBlock = 256;
+
+__global__ __launch_bounds__(kGmmBwdBlock) void gmm_params_bwd_kernel(const float* __restrict__ gamma, const float* __restrict__ pts,
+                                                                      const float* __restrict__ pi, const float* __restrict__ mu,
+                                                                      const float* __restrict__ sigma, const float* __restrict__ g_pi,
+                                                                      const float* __restrict__ g_mu, const float* __restrict__ g_sigma,
+                                                                      long long npts, int N, int J, float* __restrict__ g_logits) {
+  __shared__ float prod[kGmmBwdBlock];
+  const int P = kGmmBwdBlock / J;      // points per workgroup; lanes >= P*J idle (they still meet the barrier)
+  const int t = threadIdx.x;
+  const int slot = t / J, j = t % J;
+  const long long pt = (long long)blockIdx.x * P + slot;     // b*N + n
+  const bool live = slot < P && pt < npts;
+  float gam = 0.f, gg = 0.f;
+  if (live) {
+    const long long b = pt / N;
+    const size_t bj = (size_t)b * J + j;
+    const float* p = pts + (size_t)pt * 3;
+    const float* m = mu + bj * 3;
+    const float* gm = g_mu + bj * 3;
+    const float dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    const float s0 = pi[bj] * (float)N;
+    const float dm = (gm[0] * dx + gm[1] * dy) + gm[2] * dz;
+    gam = gamma[(size_t)pt * J + j];
+    gg = g_pi[bj] / (float)N + (dm + g_sigma[bj] * (d2 - sigma[bj])) / s0;
+  }
+  prod[t] = gam * gg;
+  __syncthreads();
+  if (live) {
+    float dot = 0.f;
+    for (int i = 0; i < J; ++i) dot += prod[slot * J + i];   // the point's J lanes add the same values in the same order
+    g_logits[(size_t)pt * J + j] = gam * (gg - dot);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Backward of gmm_register: one lane per pair, float64 registers, the forward recomputed.  The rotation's derivative takes the
+// polar form: R = V D U^T is the orthogonal polar factor of Ms^T, so with lam = (s1, s2, D33 s3) and A~ = U^T skew(R^T G_R) U,
+//   g_Ms = -2 U B~ U^T R^T,   B~_ij = A~_ij / (lam_i + lam_j)  (i != j),   skew(X) = (X - X^T) / 2.
+// The generic SVD backward divides by s_i^2 - s_j^2, which blows up at equal singular values although the terms cancel; the sums
+// lam_i + lam_j vanish only where the rotation itself is undetermined.
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kRegBlock) void gmm_register_bwd_kernel(const float* __restrict__ pi_s, const float* __restrict__ mu_s,
+                                                                     const float* __restrict__ mu_t, const float* __restrict__ sigma_t,
+                                                                     const float* __restrict__ g_T, int B, int J,
+                                                                     float* __restrict__ g_pi_s, float* __restrict__ g_mu_s,
+                                                                     float* __restrict__ g_mu_t, float* __restrict__ g_sigma_t) {
+  const int b = blockIdx.x * kRegBlock + threadIdx.x;
+  if (b >= B) return;
+  const float* w = pi_s + (size_t)b * J;
+  const float* ms = mu_s + (size_t)b * J * 3;
+  const float* mt = mu_t + (size_t)b * J * 3;
+  const float* sg = sigma_t + (size_t)b * J;
+  const float* gT = g_T + (size_t)b * 16;
+  // the forward, as gmm_register_kernel runs it
+  double cs[3] = {0., 0., 0.}, ct[3] = {0., 0., 0.};
+  for (int j = 0; j < J; ++j) {
+    const double wj = (double)w[j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { cs[i] += wj * (double)ms[3 * j + i]; ct[i] += wj * (double)mt[3 * j + i]; }
+  }
+  double M[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) M[i] = 0.;
+  for (int j = 0; j < J; ++j) {
+    const double wj = (double)w[j], inv = 1.0 / (double)sg[j];
+    double a[3], c[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { a[i] = wj * ((double)ms[3 * j + i] - cs[i]); c[i] = ((double)mt[3 * j + i] - ct[i]) * inv; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int l = 0; l < 3; ++l) M[i * 3 + l] += a[i] * c[l];
+  }
+  double U[9], S[3], V[9], VUt[9], R[9];
+  svd3x3<double>(M, U, S, V);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int l = 0; l < 3; ++l) VUt[i * 3 + l] = (V[i * 3 + 0] * U[l * 3 + 0] + V[i * 3 + 1] * U[l * 3 + 1]) + V[i * 3 + 2] * U[l * 3 + 2];
+  const double d = det3<double>(VUt);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int l = 0; l < 3; ++l) R[i * 3 + l] = (V[i * 3 + 0] * U[l * 3 + 0] + V[i * 3 + 1] * U[l * 3 + 1]) + (V[i * 3 + 2] * d) * U[l * 3 + 2];
+  const double lam[3] = {S[0], S[1], d * S[2]};
+
+  // G_R = g_T[:3,:3] - g_t c_s^T;  X = R^T G_R;  A = skew(X);  A~ = U^T A U;  B~;  g_Ms = -2 U B~ U^T R^T
+  double gt[3], GR[9], X[9], A[9], W[9], At[9], gM[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) gt[i] = (double)gT[i * 4 + 3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int l = 0; l < 3; ++l) GR[i * 3 + l] = (double)gT[i * 4 + l] - gt[i] * cs[l];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int l = 0; l < 3; ++l) X[i * 3 + l] = (R[0 * 3 + i] * GR[0 * 3 + l] + R[1 * 3 + i] * GR[1 * 3 + l]) + R[2 * 3 + i] * GR[2 * 3 + l];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int l = 0; l < 3; ++l) A[i * 3 + l] = 0.5 * (X[i * 3 + l] - X[l * 3 + i]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)          // W = A U
+#pragma unroll
+    for (int l = 0; l < 3; ++l) W[i * 3 + l] = (A[i * 3 + 0] * U[0 * 3 + l] + A[i * 3 + 1] * U[1 * 3 + l]) + A[i * 3 + 2] * U[2 * 3 + l];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)          // A~ = U^T W, then B~ in place
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {
+      const double v = (U[0 * 3 + i] * W[0 * 3 + l] + U[1 * 3 + i] * W[1 * 3 + l]) + U[2 * 3 + i] * W[2 * 3 + l];
+      At[i * 3 + l] = i == l ? 0. : v / (lam[i] + lam[l]);
+    }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)          // W = U B~
+#pragma unroll
+    for (int l = 0; l < 3; ++l) W[i * 3 + l] = (U[i * 3 + 0] * At[0 * 3 + l] + U[i * 3 + 1] * At[1 * 3 + l]) + U[i * 3 + 2] * At[2 * 3 + l];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)          // A = W U^T
+#pragma unroll
+    for (int l = 0; l < 3; ++l) A[i * 3 + l] = (W[i * 3 + 0] * U[l * 3 + 0] + W[i * 3 + 1] * U[l * 3 + 1]) + W[i * 3 + 2] * U[l * 3 + 2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)          // g_Ms = -2 A R^T
+#pragma unroll
+    for (int l = 0; l < 3; ++l) gM[i * 3 + l] = -2. * ((A[i * 3 + 0] * R[l * 3 + 0] + A[i * 3 + 1] * R[l * 3 + 1]) + A[i * 3 + 2] * R[l * 3 + 2]);
+
+  // Ms = sum_j a_j c_j^T with a_j = w_j (ms_j - c_s), c_j = (mt_j - c_t) / sg_j:  g_a_j = g_Ms c_j,  g_c_j = g_Ms^T a_j.
+  // First the two centres' totals: g_cs = -R^T g_t - sum_j w_j g_a_j,  g_ct = g_t - sum_j g_c_j / sg_j.
+  double gcs[3], gct[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    gcs[i] = -((R[0 * 3 + i] * gt[0] + R[1 * 3 + i] * gt[1]) + R[2 * 3 + i] * gt[2]);
+    gct[i] = gt[i];
+  }
+  for (int j = 0; j < J; ++j) {
+    const double wj = (double)w[j], inv = 1.0 / (double)sg[j];
+    double a[3], c[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { a[i] = wj * ((double)ms[3 * j + i] - cs[i]); c[i] = ((double)mt[3 * j + i] - ct[i]) * inv; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double ga = (gM[i * 3 + 0] * c[0] + gM[i * 3 + 1] * c[1]) + gM[i * 3 + 2] * c[2];
+      const double gc = (gM[0 * 3 + i] * a[0] + gM[1 * 3 + i] * a[1]) + gM[2 * 3 + i] * a[2];
+      gcs[i] -= wj * ga;
+      gct[i] -= gc * inv;
+    }
+  }
+  for (int j = 0; j < J; ++j) {
+    const double wj = (double)w[j], inv = 1.0 / (double)sg[j];
+    double a[3], c[3], e[3], ga[3], gc[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      e[i] = (double)ms[3 * j + i] - cs[i];
+      a[i] = wj * e[i];
+      c[i] = ((double)mt[3 * j + i] - ct[i]) * inv;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      ga[i] = (gM[i * 3 + 0] * c[0] + gM[i * 3 + 1] * c[1]) + gM[i * 3 + 2] * c[2];
+      gc[i] = (gM[0 * 3 + i] * a[0] + gM[1 * 3 + i] * a[1]) + gM[2 * 3 + i] * a[2];
+    }
+    double gw = 0., gs = 0.;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      gw += (ga[i] * e[i] + (double)ms[3 * j + i] * gcs[i]) + (double)mt[3 * j + i] * gct[i];
+      gs += gc[i] * c[i];
+      g_mu_s[((size_t)b * J + j) * 3 + i] = (float)(wj * (ga[i] + gcs[i]));
+      g_mu_t[((size_t)b * J + j) * 3 + i] = (float)(gc[i] * inv + wj * gct[i]);
+    }
+    g_pi_s[(size_t)b * J + j] = (float)gw;
+    g_sigma_t[(size_t)b * J + j] = (float)(-gs * inv);
+  }
+}
+
 }  // namespace
 }  // namespace houv
 
@@ -287,4 +466,42 @@ extern "C" int houv_gmm_register(const float* pi_s, const float* mu_s, const flo
   }
   gmm_register_kernel<<<(B + kRegBlock - 1) / kRegBlock, kRegBlock, 0, (hipStream_t)stream>>>(pi_s, mu_s, mu_t, sigma_t, B, J, T);
   return check_launch("houv_gmm_register") ? 1 : 0;
+}
+
+extern "C" int houv_gmm_params_backward(const float* gamma, const float* pts, const float* pi, const float* mu, const float* sigma,
+                                        const float* g_pi, const float* g_mu, const float* g_sigma, int B, int N, int J,
+                                        float* g_logits, void* stream) {
+  using namespace houv;
+  if (B < 0 || N <= 0 || J < 1 || J > 32 || (long long)B * N > 0x7fffffffLL) {
+    set_error("houv_gmm_params_backward: bad shape B=%d N=%d J=%d (J is 1..32)", B, N, J);
+    return 0;
+  }
+  if (B == 0) return 1;
+  if (!gamma || !pts || !pi || !mu || !sigma || !g_pi || !g_mu || !g_sigma || !g_logits) {
+    set_error("houv_gmm_params_backward: null pointer");
+    return 0;
+  }
+  const long long npts = (long long)B * N;
+  const int P = kGmmBwdBlock / J;
+  gmm_params_bwd_kernel<<<(unsigned)((npts + P - 1) / P), kGmmBwdBlock, 0, (hipStream_t)stream>>>(gamma, pts, pi, mu, sigma, g_pi, g_mu,
+                                                                                                g_sigma, npts, N, J, g_logits);
+  return check_launch("houv_gmm_params_backward") ? 1 : 0;
+}
+
+extern "C" int houv_gmm_register_backward(const float* pi_s, const float* mu_s, const float* mu_t, const float* sigma_t,
+                                          const float* g_T, int B, int J, float* g_pi_s, float* g_mu_s, float* g_mu_t,
+                                          float* g_sigma_t, void* stream) {
+  using namespace houv;
+  if (B < 0 || J < 1) {
+    set_error("houv_gmm_register_backward: bad shape B=%d J=%d", B, J);
+    return 0;
+  }
+  if (B == 0) return 1;
+  if (!pi_s || !mu_s || !mu_t || !sigma_t || !g_T || !g_pi_s || !g_mu_s || !g_mu_t || !g_sigma_t) {
+    set_error("houv_gmm_register_backward: null pointer");
+    return 0;
+  }
+  gmm_register_bwd_kernel<<<(B + kRegBlock - 1) / kRegBlock, kRegBlock, 0, (hipStream_t)stream>>>(pi_s, mu_s, mu_t, sigma_t, g_T, B, J,
+                                                                                                g_pi_s, g_mu_s, g_mu_t, g_sigma_t);
+  return check_launch("houv_gmm_register_backward") ? 1 : 0;
 }

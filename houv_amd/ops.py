@@ -375,6 +375,126 @@ def gmm_register(pi_s, mu_s, mu_t, sigma_t):
 
 
 # ---------------------------------------------------------------------------------------------------
+# DeepGMR training (houv_gmm_params_backward, houv_gmm_register_backward, houv_bn_rows_stats, houv_bn_relu_rows,
+# houv_bn_relu_rows_backward)
+# ---------------------------------------------------------------------------------------------------
+def gmm_params_backward(gamma, pts, pi, mu, sigma, g_pi, g_mu, g_sigma):
+    """The gradient of (pi, mu, sigma) = gmm_params(softmax(logits), pts) with respect to the logits, softmax backward
+    included: gamma[B,N,J], pts[B,N,3], pi / mu / sigma as gmm_params returned them, their gradients -> g_logits[B,N,J]."""
+    ts = (gamma, pts, pi, mu, sigma, g_pi, g_mu, g_sigma)
+    _lib.require_gpu(*ts)
+    for t, n in zip(ts, ("gamma", "pts", "pi", "mu", "sigma", "g_pi", "g_mu", "g_sigma")):
+        _want(t, _F32, n)
+    if gamma.dim() != 3 or pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[:2] != gamma.shape[:2]:
+        raise _lib.HouvHipError("gmm_params_backward: expected gamma[B,N,J], pts[B,N,3]")
+    B, N, J = gamma.shape
+    if any(tuple(t.shape) != (B, J) for t in (pi, sigma, g_pi, g_sigma)) or any(tuple(t.shape) != (B, J, 3) for t in (mu, g_mu)):
+        raise _lib.HouvHipError("gmm_params_backward: expected pi / sigma and their gradients [B,J], mu / g_mu [B,J,3]")
+    g_logits = torch.empty_like(gamma)
+    with torch.cuda.device(gamma.device):
+        ok = _lib.load().houv_gmm_params_backward(*[_lib.ptr(t) for t in ts], B, N, J, _lib.ptr(g_logits), _lib.stream_of(gamma))
+    _lib.check(ok, "houv_gmm_params_backward")
+    return g_logits
+
+
+def gmm_register_backward(pi_s, mu_s, mu_t, sigma_t, g_T):
+    """The gradient of T = gmm_register(pi_s, mu_s, mu_t, sigma_t): g_T[B,4,4] -> (g_pi_s[B,J], g_mu_s[B,J,3], g_mu_t[B,J,3],
+    g_sigma_t[B,J]); the polar form of the rotation's derivative, in float64 registers."""
+    ts = (pi_s, mu_s, mu_t, sigma_t, g_T)
+    _lib.require_gpu(*ts)
+    for t, n in zip(ts, ("pi_s", "mu_s", "mu_t", "sigma_t", "g_T")):
+        _want(t, _F32, n)
+    if pi_s.dim() != 2 or tuple(mu_s.shape) != tuple(pi_s.shape) + (3,) or mu_t.shape != mu_s.shape or sigma_t.shape != pi_s.shape \
+            or tuple(g_T.shape) != (pi_s.shape[0], 4, 4):
+        raise _lib.HouvHipError("gmm_register_backward: expected pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J], g_T[B,4,4]")
+    B, J = pi_s.shape
+    outs = (torch.empty_like(pi_s), torch.empty_like(mu_s), torch.empty_like(mu_t), torch.empty_like(sigma_t))
+    with torch.cuda.device(pi_s.device):
+        ok = _lib.load().houv_gmm_register_backward(*[_lib.ptr(t) for t in ts], B, J, *[_lib.ptr(t) for t in outs],
+                                                    _lib.stream_of(pi_s))
+    _lib.check(ok, "houv_gmm_register_backward")
+    return outs
+
+
+def _bn_rows(z, name):
+    """(R, C, ld) of rows z[R,C]: a row-major view whose columns are contiguous (a column slice of a wider buffer is fine)."""
+    _lib.require_gpu_any(z)
+    if z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1 or z.stride(1) != 1 or z.stride(0) < z.shape[1]:
+        raise _lib.HouvHipError(f"{name}: expected rows [R,C] with contiguous columns and a row stride >= C")
+    return z.shape[0], z.shape[1], z.stride(0)
+
+
+def _bn_vectors(C, *vs):
+    for v in vs:
+        _lib.require_gpu(v); _want(v, _F32, "per-channel vector")
+        if tuple(v.shape) != (C,):
+            raise _lib.HouvHipError(f"bn_rows: expected per-channel vectors of {C} elements")
+
+
+def _bn_workspace(R, C, n_group, device):
+    nbytes = _lib.load().houv_bn_rows_workspace_bytes(R, C, n_group)
+    return torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=device), nbytes
+
+
+def bn_rows_stats(z):
+    """z[R,C] (R >= 2, any row stride) -> (mean[C], var[C]): the batch statistics of training-mode BatchNorm, var biased about
+    the mean.  Ordered sums: the same bits from call to call."""
+    R, C, ld = _bn_rows(z, "bn_rows_stats")
+    mean = torch.empty((C,), dtype=_F32, device=z.device)
+    var = torch.empty((C,), dtype=_F32, device=z.device)
+    ws, nbytes = _bn_workspace(R, C, 0, z.device)
+    with torch.cuda.device(z.device):
+        ok = _lib.load().houv_bn_rows_stats(ctypes_ptr(z), R, C, ld, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(ws), nbytes,
+                                            _lib.stream_of(z))
+    _lib.check(ok, "houv_bn_rows_stats")
+    return mean, var
+
+
+def bn_relu_rows(z, mean, var, weight, bias, eps=1e-5, relu=True, n_group=0):
+    """y[R,C] = relu?((z - mean) * rsqrt(var + eps) * weight + bias).  With n_group > 0 (a divisor of R) returns
+    (y, gmax[R/n_group,C], garg[R/n_group,C] int32): the column maximum of y over each group of n_group rows and the lowest row
+    index, counted over all R rows, that attains it -- a cloud's max-pool from the same read."""
+    R, C, ld = _bn_rows(z, "bn_relu_rows")
+    _bn_vectors(C, mean, var, weight, bias)
+    n_group = int(n_group)
+    if n_group < 0 or (n_group and R % n_group):
+        raise _lib.HouvHipError(f"bn_relu_rows: n_group = {n_group} does not divide the {R} rows")
+    y = torch.empty((R, C), dtype=_F32, device=z.device)
+    gmax = garg = None
+    if n_group:
+        gmax = torch.empty((R // n_group, C), dtype=_F32, device=z.device)
+        garg = torch.empty((R // n_group, C), dtype=_I32, device=z.device)
+    ws, nbytes = _bn_workspace(R, C, n_group, z.device)
+    with torch.cuda.device(z.device):
+        ok = _lib.load().houv_bn_relu_rows(ctypes_ptr(z), R, C, ld, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(weight), _lib.ptr(bias),
+                                           float(eps), int(bool(relu)), n_group, _lib.ptr(y), C, _lib.ptr(gmax), _lib.ptr(garg),
+                                           _lib.ptr(ws), nbytes, _lib.stream_of(z))
+    _lib.check(ok, "houv_bn_relu_rows")
+    return (y, gmax, garg) if n_group else y
+
+
+def bn_relu_rows_backward(gy, z, mean, var, weight, bias, eps=1e-5, relu=True, inplace=False):
+    """The backward of bn_relu_rows under batch statistics: gy[R,C] -> (gz[R,C], gweight[C], gbias[C]); the ReLU mask and xhat
+    are recomputed from z.  inplace: gz overwrites gy."""
+    R, C, ld = _bn_rows(z, "bn_relu_rows_backward")
+    Rg, Cg, ldg = _bn_rows(gy, "bn_relu_rows_backward")
+    if (Rg, Cg) != (R, C):
+        raise _lib.HouvHipError("bn_relu_rows_backward: gy and z differ in shape")
+    _bn_vectors(C, mean, var, weight, bias)
+    gz = gy if inplace else torch.empty((R, C), dtype=_F32, device=z.device)
+    gweight = torch.empty((C,), dtype=_F32, device=z.device)
+    gbias = torch.empty((C,), dtype=_F32, device=z.device)
+    ws, nbytes = _bn_workspace(R, C, 0, z.device)
+    with torch.cuda.device(z.device):
+        ok = _lib.load().houv_bn_relu_rows_backward(ctypes_ptr(gy), ldg, ctypes_ptr(z), R, C, ld, _lib.ptr(mean), _lib.ptr(var),
+                                                    _lib.ptr(weight), _lib.ptr(bias), float(eps), int(bool(relu)), ctypes_ptr(gz),
+                                                    gz.stride(0), _lib.ptr(gweight), _lib.ptr(gbias), _lib.ptr(ws), nbytes,
+                                                    _lib.stream_of(z))
+    _lib.check(ok, "houv_bn_relu_rows_backward")
+    return gz, gweight, gbias
+
+
+# ---------------------------------------------------------------------------------------------------
 # IDAM head (houv_idam_simmat, houv_edge_diff; DESIGN.md section 9.8)
 # ---------------------------------------------------------------------------------------------------
 def idam_simmat(src, tgt, es, et, W1, s1, t1, W2, b2, W3, s3, t3, w4, b4, want_rowmax=True, want_idx=True, want_corr=True,
@@ -1028,6 +1148,15 @@ def register_torch_ops():
     lib.define("rri_features(Tensor xyz, Tensor idx, int k, int skip) -> Tensor")
     lib.define("gmm_params(Tensor gamma, Tensor pts) -> (Tensor, Tensor, Tensor)")
     lib.define("gmm_register(Tensor pi_s, Tensor mu_s, Tensor mu_t, Tensor sigma_t) -> Tensor")
+    lib.define("gmm_params_backward(Tensor gamma, Tensor pts, Tensor pi, Tensor mu, Tensor sigma, Tensor g_pi, Tensor g_mu, "
+               "Tensor g_sigma) -> Tensor")
+    lib.define("gmm_register_backward(Tensor pi_s, Tensor mu_s, Tensor mu_t, Tensor sigma_t, Tensor g_T) -> "
+               "(Tensor, Tensor, Tensor, Tensor)")
+    lib.define("bn_rows_stats(Tensor z) -> (Tensor, Tensor)")
+    lib.define("bn_relu_rows(Tensor z, Tensor mean, Tensor var, Tensor weight, Tensor bias, float eps, bool relu, int n_group) -> "
+               "(Tensor, Tensor, Tensor)")
+    lib.define("bn_relu_rows_backward(Tensor gy, Tensor z, Tensor mean, Tensor var, Tensor weight, Tensor bias, float eps, "
+               "bool relu) -> (Tensor, Tensor, Tensor)")
     lib.define("idam_simmat(Tensor src, Tensor tgt, Tensor es, Tensor et, Tensor W1, Tensor s1, Tensor t1, Tensor W2, Tensor b2, "
                "Tensor W3, Tensor s3, Tensor t3, Tensor w4, Tensor b4) -> (Tensor, Tensor, Tensor, Tensor)")
     lib.define("edge_diff(Tensor x, Tensor idx, int k, int ldo) -> Tensor")
@@ -1068,6 +1197,15 @@ def register_torch_ops():
     lib.impl("rri_features", rri_features, "CUDA")
     lib.impl("gmm_params", gmm_params, "CUDA")
     lib.impl("gmm_register", gmm_register, "CUDA")
+    lib.impl("gmm_params_backward", gmm_params_backward, "CUDA")
+    lib.impl("gmm_register_backward", gmm_register_backward, "CUDA")
+    lib.impl("bn_rows_stats", bn_rows_stats, "CUDA")
+
+    def _bn_relu_rows(z, mean, var, weight, bias, eps, relu, n_group):
+        r = bn_relu_rows(z, mean, var, weight, bias, eps, relu, n_group)
+        return r if n_group else (r, z.new_empty((0, z.shape[1])), z.new_empty((0, z.shape[1]), dtype=_I32))
+    lib.impl("bn_relu_rows", _bn_relu_rows, "CUDA")
+    lib.impl("bn_relu_rows_backward", bn_relu_rows_backward, "CUDA")
 
     def _simmat(*a):
         return idam_simmat(*a, want_scores=True)

@@ -423,6 +423,61 @@ int houv_gmm_register(const float* pi_s, const float* mu_s, const float* mu_t, c
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * DeepGMR training: the backward of the two GMM kernels above, and training-mode BatchNorm on
+ * point-major rows.  fp32 data, fixed expression trees, no allocation, no float atomics: every sum runs in an order fixed by
+ * the shape, so results are bit-identical from call to call.  Each returns 0 with houv_last_error() set, launching nothing,
+ * when a check fails. */
+
+/* Backward of (pi, mu, sigma) = houv_gmm_params(gamma = softmax(logits), pts) with the softmax's folded in.  gamma[B,N,J],
+ * pts[B,N,3], pi / mu / sigma as houv_gmm_params returned them, g_pi[B,J], g_mu[B,J,3], g_sigma[B,J]; 1 <= J <= 32.
+ * With S0_j = N pi_j and d = p_n - mu_j:
+ *   gg[n,j]       = g_pi_j / N + ((g_mu_j . d) + g_sigma_j (|d|^2 - sigma_j)) / S0_j
+ *   g_logits[n,j] = gamma[n,j] (gg[n,j] - sum_i gamma[n,i] gg[n,i])
+ * One pass, one point per group of J lanes; nothing of size [B,N,J,3] is built.  pts gets no gradient. */
+int houv_gmm_params_backward(const float* gamma, const float* pts, const float* pi, const float* mu, const float* sigma,
+                             const float* g_pi, const float* g_mu, const float* g_sigma, int B, int N, int J, float* g_logits,
+                             void* stream);
+
+/* Backward of T = houv_gmm_register(pi_s, mu_s, mu_t, sigma_t): g_T[B,4,4] (its bottom row is ignored) -> g_pi_s[B,J],
+ * g_mu_s[B,J,3], g_mu_t[B,J,3], g_sigma_t[B,J].  One lane per pair, float64 registers, the forward recomputed.  The rotation's
+ * derivative is taken in polar form, not through the SVD's (whose 1 / (s_i^2 - s_j^2) terms blow up at equal singular values
+ * although they cancel): with Ms = U S V^T, R = V D U^T, D = diag(1, 1, det(V U^T)), lam = (s1, s2, D33 s3),
+ *   G_R = g_T[:3,:3] - g_t c_s^T,   A~ = U^T skew(R^T G_R) U,   B~_ij = A~_ij / (lam_i + lam_j) (i != j),   skew(X) = (X - X^T)/2
+ *   g_Ms = -2 U B~ U^T R^T;   g_c_t = g_t,   g_c_s = -R^T g_t
+ * and the chain through Ms, c_s, c_t (pi_s weights both centres) gives the four outputs.  A pair with lam_i + lam_j = 0 (the
+ * rotation is then undetermined) yields inf/NaN. */
+int houv_gmm_register_backward(const float* pi_s, const float* mu_s, const float* mu_t, const float* sigma_t, const float* g_T,
+                               int B, int J, float* g_pi_s, float* g_mu_s, float* g_mu_t, float* g_sigma_t, void* stream);
+
+/* Training-mode BatchNorm over rows z[R,C] with row stride ld >= C (floats); C >= 1.  Rows are handled in chunks of 128: a
+ * chunk's column sums are formed by one workgroup in a fixed order, written to the workspace and combined in chunk order by a
+ * second launch.  workspace: houv_bn_rows_workspace_bytes(R, C, N_group) bytes (0 for arguments out of range), 16-byte aligned;
+ * its contents are scratch.  16-byte loads are used where C, the strides and the pointers are multiples of 4 floats.
+ *
+ * houv_bn_rows_stats (R >= 2): mean[C] and the biased variance var[C] about it; per chunk (mean, M2) by two passes, chunks
+ * merged as (count, mean, M2) -- never E[z^2] - mean^2. */
+long long houv_bn_rows_workspace_bytes(long long R, int C, int N_group);
+int houv_bn_rows_stats(const float* z, long long R, int C, long long ld, float* mean, float* var, void* workspace,
+                       long long workspace_bytes, void* stream);
+
+/* y[R,C] (row stride ldy) = relu?(((z - mean) * rstd) * weight + bias), rstd = 1 / sqrt(var + eps).  With
+ * N_group > 0 (it must divide R) also gmax[R/N_group, C] and garg[R/N_group, C]: the column maximum of y over each group of
+ * N_group consecutive rows and the lowest row index (0 <= garg < R, counted over all rows) that attains it; NaN never attains
+ * a maximum.  The workspace is needed for N_group > 128 only and may be NULL otherwise. */
+int houv_bn_relu_rows(const float* z, long long R, int C, long long ld, const float* mean, const float* var, const float* weight,
+                      const float* bias, float eps, int relu, int N_group, float* y, long long ldy, float* gmax, int32_t* garg,
+                      void* workspace, long long workspace_bytes, void* stream);
+
+/* Backward of houv_bn_relu_rows with mean / var the batch statistics of z: gy[R,C] (row stride ldg) -> gz[R,C] (row stride
+ * ldz), gweight[C], gbias[C].  xhat and the ReLU mask are recomputed from z with the forward's expression; g = gy [y > 0];
+ *   gbias = sum_r g,  gweight = sum_r g xhat,  gz = (weight rstd) ((g - gbias / R) - xhat (gweight / R)).
+ * gz may be gy. */
+int houv_bn_relu_rows_backward(const float* gy, long long ldg, const float* z, long long R, int C, long long ld, const float* mean,
+                               const float* var, const float* weight, const float* bias, float eps, int relu, float* gz,
+                               long long ldz, float* gweight, float* gbias, void* workspace, long long workspace_bytes,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * IDAM head (registration/models/idam.py).  fp32 data, fixed expression trees, no allocation, no atomics:
  * results are bit-identical from call to call.  Each returns 0 with houv_last_error() set, launching nothing, when a check
  * fails. */
