@@ -115,6 +115,27 @@ _SIGNATURES = {
     "houv_pose_forward": (ctypes.c_int,[_c_f, _int, _int, _int, _c_f, _int, _c_f, _c_f, _c_f, _c_f]),
 }
 
+
+def _addresses(kinds):
+    """A function compiled for one entry: its arguments in, the same out with the tensors of the pointer slots as addresses.
+    Generated source, not a loop over the pointer slots' indices: on a stub library the loop cost houv_knn's launch 2.96 us
+    against 2.7 us for this form and 2.5 us for the four inline lines it replaces, and this form is the one whose per-call and
+    bench.py figures lie inside the parent's spread (profiles/r17_ops_call_path.txt)."""
+    names = [f"a{i}" for i in range(len(kinds))]
+    items = [f"{n} if {n} is None else {n}.data_ptr()" if k is None else n for n, k in zip(names, kinds)]
+    return eval(f"lambda {', '.join(names)}: ({', '.join(items)},)")
+
+
+# What `call` needs of every launching entry, worked out once: the kind of each slot before the stream (None: pointer, int,
+# float) and the entry's _addresses.  INVARIANT of _SIGNATURES: an entry launches if and only if its last slot is a c_void_p,
+# and that slot is the stream; size and variant queries end in a scalar or a typed POINTER and are called directly.
+_SLOTS = {}
+for _name, (_, _args) in _SIGNATURES.items():
+    if _args and _args[-1] is _c_f:
+        _kinds = tuple(None if c is _c_f else float if c in (_flt, _dbl) else int for c in _args[:-1])
+        _SLOTS[_name] = (_kinds, _addresses(_kinds))
+_PLAIN = frozenset((int, float, bool, type(None)))      # what ctypes converts by itself once the tensors are addresses
+
 _lib = None
 
 
@@ -191,7 +212,62 @@ def stream_of(t):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def require_gpu(*tensors, dtype=None):
+def call(name, on, *args):
+    """Launch entry `name` on the torch current stream of tensor `on`'s device and check its result.  Each argument is converted
+    by its slot's type in _SIGNATURES: a pointer slot takes a tensor (its address), None (NULL) or a c_void_p; an integer slot
+    int() (True / False arrive as 1 / 0; a value with a fraction is refused); a float slot float().  The stream is appended
+    here.  This is the host cost of every launch, so the usual case -- tensors or None in the pointer slots, plain Python
+    numbers elsewhere -- touches the pointer slots only and leaves the numbers to ctypes; anything else takes _checked."""
+    kinds, addresses = _SLOTS[name]
+    if len(args) != len(kinds):
+        raise TypeError(f"{name}: takes {len(kinds)} arguments before the stream, got {len(args)}")
+    try:
+        conv = addresses(*args)
+        if not _PLAIN.issuperset(map(type, conv)):      # a tensor in a scalar slot, a numpy number, a c_void_p, ...
+            conv = _checked(name, kinds, args)
+    except AttributeError:                              # something else than a tensor in a pointer slot
+        conv = _checked(name, kinds, args)
+    fn = getattr(_lib or load(), name)
+    with torch.cuda.device(on.device):
+        stream = stream_of(on)
+        try:
+            ok = fn(*conv, stream)
+        except ctypes.ArgumentError:                    # a float in an integer slot
+            ok = fn(*_checked(name, kinds, args), stream)
+    if ok != 1:
+        check(ok, name)
+
+
+def _checked(name, kinds, args):
+    """call's arguments converted one by one, every refusal naming the entry and the slot."""
+    conv = []
+    for i, (kind, a) in enumerate(zip(kinds, args)):
+        if kind is None:
+            if isinstance(a, torch.Tensor):
+                a = a.data_ptr()
+            elif a is not None and not isinstance(a, ctypes.c_void_p):
+                raise TypeError(f"{name}: argument {i} is a pointer: expected a tensor, None or a c_void_p, got {type(a).__name__}")
+        elif isinstance(a, torch.Tensor):
+            raise TypeError(f"{name}: argument {i} is a scalar ({kind.__name__}), got a tensor")
+        elif kind is int and int(a) != a:
+            raise TypeError(f"{name}: argument {i} is an integer, got {a!r}")
+        else:
+            a = kind(a)
+        conv.append(a)
+    return conv
+
+
+def workspace(bytes_entry, device, *dims, floor=16):
+    """(workspace, nbytes) for the size query `bytes_entry`(*dims): a fresh uint8 allocation of max(nbytes, floor) bytes.
+    floor=0 is what selects NULL: the allocation is then exactly nbytes, and None (the library's NULL) when the query says 0;
+    with the default floor there is always an allocation.  nbytes is what the query returned: the figure the entries that
+    take one are told."""
+    nbytes = getattr(load(), bytes_entry)(*map(int, dims))
+    size = max(nbytes, floor)
+    return (torch.empty(size, dtype=torch.uint8, device=device) if size > 0 else None), nbytes
+
+
+def require_gpu(*tensors):
     for t in tensors:
         if t is None:
             continue

@@ -36,10 +36,7 @@ def furthest_point_sample(points_xyz, num_points):
     pts = _f32(points_xyz, "points_xyz")                 # kept alive in a local until the launch is enqueued
     B, N, _ = pts.shape
     out = torch.empty((B, num_points), dtype=_I32, device=pts.device)
-    with torch.cuda.device(pts.device):
-        ok = _lib.load().houv_furthest_point_sample(_lib.ptr(pts), B, N, int(num_points), _lib.ptr(out),
-                                                    _lib.stream_of(pts))
-    _lib.check(ok, "houv_furthest_point_sample")
+    _lib.call("houv_furthest_point_sample", pts, pts, B, N, num_points, out)
     return out
 
 
@@ -50,13 +47,9 @@ def _scatter_grad(grad_out, idx, weight, N, S):
         grad_out = grad_out.float()
     B, C, _ = grad_out.shape
     M = idx.shape[1]
-    lib = _lib.load()
-    ws = torch.empty(lib.houv_scatter_points_workspace_bytes(B, N, M), dtype=torch.uint8, device=grad_out.device)
+    ws = _lib.workspace("houv_scatter_points_workspace_bytes", grad_out.device, B, N, M, floor=0)[0]
     grad = torch.empty((B, C, N), dtype=_F32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        ok = lib.houv_scatter_points_grad(_lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(weight), B, C, N, M, S, _lib.ptr(grad),
-                                          _lib.ptr(ws), _lib.stream_of(grad_out))
-    _lib.check(ok, "houv_scatter_points_grad")
+    _lib.call("houv_scatter_points_grad", grad_out, grad_out, idx, weight, B, C, N, M, S, grad, ws)
     return grad
 
 
@@ -65,10 +58,7 @@ def _gather_forward(feats, idx):
     B, C, N = feats.shape
     M = idx.shape[1]
     out = torch.empty((B, C, M), dtype=_F32, device=feats.device)
-    with torch.cuda.device(feats.device):
-        ok = _lib.load().houv_gather_points(_lib.ptr(feats), _lib.ptr(idx), B, C, N, M, _lib.ptr(out),
-                                            _lib.stream_of(feats))
-    _lib.check(ok, "houv_gather_points")
+    _lib.call("houv_gather_points", feats, feats, idx, B, C, N, M, out)
     return out
 
 
@@ -95,10 +85,7 @@ class _ThreeInterpolate(torch.autograd.Function):
         ctx.save_for_backward(idx, weight)
         ctx.M = M
         out = torch.empty((B, C, N), dtype=_F32, device=feats.device)
-        with torch.cuda.device(feats.device):
-            ok = _lib.load().houv_three_interpolate(_lib.ptr(feats), _lib.ptr(idx), _lib.ptr(weight), B, C, M, N, _lib.ptr(out),
-                                                    _lib.stream_of(feats))
-        _lib.check(ok, "houv_three_interpolate")
+        _lib.call("houv_three_interpolate", feats, feats, idx, weight, B, C, M, N, out)
         return out
 
     @staticmethod
@@ -160,10 +147,7 @@ def ball_query(min_radius, max_radius, sample_num, xyz, center_xyz, return_count
     Mc = ctr.shape[1]
     idx = torch.empty((B, Mc, int(sample_num)), dtype=_I32, device=pts.device)
     cnt = torch.empty((B, Mc), dtype=_I32, device=pts.device) if return_count else None
-    with torch.cuda.device(pts.device):
-        ok = _lib.load().houv_ball_query(_lib.ptr(pts), _lib.ptr(ctr), B, N, Mc, float(min_radius), float(max_radius),
-                                         int(sample_num), _lib.ptr(idx), _lib.ptr(cnt), _lib.stream_of(pts))
-    _lib.check(ok, "houv_ball_query")
+    _lib.call("houv_ball_query", pts, pts, ctr, B, N, Mc, min_radius, max_radius, sample_num, idx, cnt)
     return (idx, cnt) if return_count else idx
 
 
@@ -178,10 +162,7 @@ def knn_cross(k, query, ref):
     B, N, _ = q.shape
     d2 = torch.empty((B, N, int(k)), dtype=_F32, device=q.device)
     idx = torch.empty((B, N, int(k)), dtype=_I32, device=q.device)
-    with torch.cuda.device(q.device):
-        ok = _lib.load().houv_knn_cross(_lib.ptr(q), _lib.ptr(r), B, N, r.shape[1], int(k), _lib.ptr(d2), _lib.ptr(idx),
-                                        _lib.stream_of(q))
-    _lib.check(ok, "houv_knn_cross")
+    _lib.call("houv_knn_cross", q, q, r, B, N, r.shape[1], k, d2, idx)
     return d2, idx
 
 
@@ -196,10 +177,7 @@ def three_nn(target, source):
     M = source.shape[1]
     d2 = torch.empty((B, N, 3), dtype=_F32, device=target.device)
     idx = torch.empty((B, N, 3), dtype=_I32, device=target.device)
-    with torch.cuda.device(target.device):
-        ok = _lib.load().houv_knn_cross(_lib.ptr(target), _lib.ptr(source), B, N, M, 3, _lib.ptr(d2), _lib.ptr(idx),
-                                        _lib.stream_of(target))
-    _lib.check(ok, "houv_knn_cross")
+    _lib.call("houv_knn_cross", target, target, source, B, N, M, 3, d2, idx)
     return torch.sqrt(d2), idx
 
 

@@ -25,10 +25,7 @@ def chamfer_forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
         raise _lib.HouvHipError("chamfer_forward: expected xyz1[B,N,3], xyz2[B,M,3]")
     if dist1.numel() != B * N or idx1.numel() != B * N or dist2.numel() != B * M or idx2.numel() != B * M:
         raise _lib.HouvHipError("chamfer_forward: output shapes do not match [B,N] / [B,M]")
-    with torch.cuda.device(xyz1.device):
-        ok = _lib.load().houv_chamfer_forward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, N, M, _lib.ptr(dist1), _lib.ptr(dist2),
-                                              _lib.ptr(idx1), _lib.ptr(idx2), _lib.stream_of(xyz1))
-    _lib.check(ok, "houv_chamfer_forward")
+    _lib.call("houv_chamfer_forward", xyz1, xyz1, xyz2, B, N, M, dist1, dist2, idx1, idx2)
     return 1
 
 
@@ -45,11 +42,7 @@ def chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
     if (gradxyz1.shape != xyz1.shape or gradxyz2.shape != xyz2.shape or graddist1.numel() != B * N
             or graddist2.numel() != B * M or idx1.numel() != B * N or idx2.numel() != B * M):
         raise _lib.HouvHipError("chamfer_backward: shape mismatch")
-    with torch.cuda.device(xyz1.device):
-        ok = _lib.load().houv_chamfer_backward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, N, M, _lib.ptr(graddist1),
-                                               _lib.ptr(graddist2), _lib.ptr(idx1), _lib.ptr(idx2), _lib.ptr(gradxyz1),
-                                               _lib.ptr(gradxyz2), _lib.stream_of(xyz1))
-    _lib.check(ok, "houv_chamfer_backward")
+    _lib.call("houv_chamfer_backward", xyz1, xyz1, xyz2, B, N, M, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2)
     return 1
 
 
@@ -67,10 +60,7 @@ def kabsch(src, corr, weights=None):
             raise _lib.HouvHipError("kabsch: expected weights [B,1,N]")
     R = torch.empty((B, 3, 3), dtype=_F32, device=src.device)
     t = torch.empty((B, 3), dtype=_F32, device=src.device)
-    with torch.cuda.device(src.device):
-        ok = _lib.load().houv_kabsch(_lib.ptr(src), _lib.ptr(corr), _lib.ptr(weights), B, N, _lib.ptr(R), _lib.ptr(t),
-                                     _lib.stream_of(src))
-    _lib.check(ok, "houv_kabsch")
+    _lib.call("houv_kabsch", src, src, corr, weights, B, N, R, t)
     return R, t
 
 
@@ -86,11 +76,21 @@ def pose_forward(params, angle_base, trans_mode=0, src=None):
         _want(src, _F32, "src")
         N = src.shape[1]
         moved = torch.empty_like(src)
-    with torch.cuda.device(params.device):
-        ok = _lib.load().houv_pose_forward(_lib.ptr(params), n, int(angle_base), int(trans_mode), _lib.ptr(src), N,
-                                           _lib.ptr(R), _lib.ptr(T), _lib.ptr(moved), _lib.stream_of(params))
-    _lib.check(ok, "houv_pose_forward")
+    _lib.call("houv_pose_forward", params, params, n, angle_base, trans_mode, src, N, R, T, moved)
     return (R, T) if src is None else (R, T, moved)
+
+
+def _solve_args(who, src, tgt, state, K):
+    """(P, N, M, P*K) of the solve entries' clouds src[P,N,3], tgt[P,M,3] and state [P*K,24] fp64."""
+    _want(src, _F32, "src"); _want(tgt, _F32, "tgt"); _want(state, _F64, "state")
+    P, N, _ = src.shape
+    M = tgt.shape[1]
+    if tgt.shape[0] != P or src.shape[2] != 3 or tgt.shape[2] != 3:
+        raise _lib.HouvHipError(f"{who}: expected src[P,N,3], tgt[P,M,3]")
+    n = P * int(K)
+    if tuple(state.shape) != (n, 24):
+        raise _lib.HouvHipError(f"{who}: state must be [{n},24], got {tuple(state.shape)}")
+    return P, N, M, n
 
 
 def _want_nn_ws(nn_ws, n, who):
@@ -109,24 +109,13 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
     With ``sched_ws`` (solve_sched_workspace) the call is ``houv_solve_stage[_pruned]``: ``n_iters`` is a whole stage, run in one
     launch as items of ``chunk_iters`` iterations.  Returns 1."""
     _lib.require_gpu(src, tgt, state, out_score, out_loss, out_R, out_T, out_grad, out_cd, nn_ws, sched_ws)
-    _want(src, _F32, "src"); _want(tgt, _F32, "tgt"); _want(state, _F64, "state")
-    P, N, _ = src.shape
-    M = tgt.shape[1]
-    if tgt.shape[0] != P or src.shape[2] != 3 or tgt.shape[2] != 3:
-        raise _lib.HouvHipError("solve_iterate: expected src[P,N,3], tgt[P,M,3]")
-    n = P * int(K)
-    if tuple(state.shape) != (n, 24):
-        raise _lib.HouvHipError(f"solve_iterate: state must be [{n},24], got {tuple(state.shape)}")
+    P, N, M, n = _solve_args("solve_iterate", src, tgt, state, K)
     for t, numel, name in ((out_score, n, "out_score"), (out_loss, n, "out_loss"), (out_R, 9 * n, "out_R"),
                            (out_T, 3 * n, "out_T"), (out_grad, 8 * n, "out_grad"), (out_cd, 8 * n, "out_cd")):
         if t is not None:
             _want(t, _F32, name)
             if t.numel() != numel:
                 raise _lib.HouvHipError(f"solve_iterate: {name} must hold {numel} floats, got {t.numel()}")
-    common = (_lib.ptr(src), _lib.ptr(tgt), P, N, M, int(K), _lib.ptr(state), int(steps_done), int(n_iters),
-              int(angle_base), int(trans_mode), int(bool(use_views)), int(bool(f64_params)), int(k_full), int(k_view),
-              float(lr), float(beta1), float(beta2), float(eps), float(loss_scale), _lib.ptr(out_score),
-              _lib.ptr(out_loss), _lib.ptr(out_R), _lib.ptr(out_T), _lib.ptr(out_grad), _lib.ptr(out_cd))
     stage = sched_ws is not None
     if large and nn_ws is not None:
         raise _lib.HouvHipError("solve_iterate: the large-cloud kernel is a brute-force sweep and takes no workspace")
@@ -135,14 +124,14 @@ def solve_iterate_out(src, tgt, state, K, steps_done, n_iters, angle_base, trans
     name = ("houv_solve_stage" if stage else "houv_solve_iterate") + ("_large" if large else "_pruned" if nn_ws is not None else "")
     if stage and (sched_ws.dtype != torch.int32 or sched_ws.numel() < 4 + n):
         raise _lib.HouvHipError(f"solve_iterate: sched_ws must hold {4 + n} int32 (ops.solve_sched_workspace)")
+    ws = sched = ()         # the tails the entry has: _lib._SOLVE_WS, _lib._SOLVE_SCHED
     if nn_ws is not None:   # exact pruned search: nn_ws int16 [P*K, 16, stride] (solve_workspace) persists between chunked launches
         _want_nn_ws(nn_ws, n, "solve_iterate")
-        common += (_lib.ptr(nn_ws), int(ws_valid), nn_ws.shape[2])
+        ws = (nn_ws, ws_valid, nn_ws.shape[2])
     if stage:
-        common += (int(chunk_iters), _lib.ptr(sched_ws))
-    with torch.cuda.device(src.device):
-        ok = getattr(_lib.load(), name)(*common, _lib.stream_of(src))
-    _lib.check(ok, name)
+        sched = (chunk_iters, sched_ws)
+    _lib.call(name, src, src, tgt, P, N, M, K, state, steps_done, n_iters, angle_base, trans_mode, bool(use_views), bool(f64_params),
+              k_full, k_view, lr, beta1, beta2, eps, loss_scale, out_score, out_loss, out_R, out_T, out_grad, out_cd, *ws, *sched)
     return 1
 
 
@@ -169,20 +158,9 @@ def solve_seed(src, tgt, state, K, angle_base, trans_mode, use_views, nn_ws):
     (solve_workspace), so that the next solve_iterate on them may start with ``ws_valid=True``: its first iteration then runs the
     pruned search instead of the brute-force sweep, with the same results.  Clouds of 257..4096 points.  Returns 1."""
     _lib.require_gpu(src, tgt, state, nn_ws)
-    _want(src, _F32, "src"); _want(tgt, _F32, "tgt"); _want(state, _F64, "state")
-    P, N, _ = src.shape
-    M = tgt.shape[1]
-    if tgt.shape[0] != P or src.shape[2] != 3 or tgt.shape[2] != 3:
-        raise _lib.HouvHipError("solve_seed: expected src[P,N,3], tgt[P,M,3]")
-    n = P * int(K)
-    if tuple(state.shape) != (n, 24):
-        raise _lib.HouvHipError(f"solve_seed: state must be [{n},24], got {tuple(state.shape)}")
+    P, N, M, n = _solve_args("solve_seed", src, tgt, state, K)
     _want_nn_ws(nn_ws, n, "solve_seed")
-    with torch.cuda.device(src.device):
-        ok = _lib.load().houv_solve_seed(_lib.ptr(src), _lib.ptr(tgt), P, N, M, int(K), _lib.ptr(state), int(angle_base),
-                                         int(trans_mode), int(bool(use_views)), _lib.ptr(nn_ws), nn_ws.shape[2],
-                                         _lib.stream_of(src))
-    _lib.check(ok, "houv_solve_seed")
+    _lib.call("houv_solve_seed", src, src, tgt, P, N, M, K, state, angle_base, trans_mode, bool(use_views), nn_ws, nn_ws.shape[2])
     return 1
 
 
@@ -229,10 +207,7 @@ def kd_sort(cloud, leaf=32, rule="area", return_order=False):
     P, N, _ = cloud.shape
     out = torch.empty_like(cloud)
     order = torch.empty((P, N), dtype=_I32, device=cloud.device) if return_order else None
-    with torch.cuda.device(cloud.device):
-        ok = _lib.load().houv_kd_sort(_lib.ptr(cloud), P, N, int(leaf), KD_RULES[rule], _lib.ptr(out), _lib.ptr(order),
-                                      _lib.stream_of(cloud))
-    _lib.check(ok, "houv_kd_sort")
+    _lib.call("houv_kd_sort", cloud, cloud, P, N, leaf, KD_RULES[rule], out, order)
     return (out, order) if return_order else out
 
 
@@ -255,20 +230,15 @@ def icp_refine(src, tgt, init=None, max_correspondence_distance=0.02, max_iterat
     fit = torch.empty(P, dtype=_F32, device=dev)
     rmse = torch.empty(P, dtype=_F32, device=dev)
     iters = torch.empty(P, dtype=_I32, device=dev)
-    with torch.cuda.device(dev):
-        ok = _lib.load().houv_icp_refine(_lib.ptr(src), _lib.ptr(tgt), P, N, M, _lib.ptr(init),
-                                         float(max_correspondence_distance), int(max_iteration), float(relative_fitness),
-                                         float(relative_rmse), _lib.ptr(T), _lib.ptr(fit), _lib.ptr(rmse),
-                                         _lib.ptr(iters), _lib.stream_of(src))
-    _lib.check(ok, "houv_icp_refine")
+    _lib.call("houv_icp_refine", src, src, tgt, P, N, M, init, max_correspondence_distance, max_iteration, relative_fitness,
+              relative_rmse, T, fit, rmse, iters)
     return dict(T=T, fitness=fit, inlier_rmse=rmse, iterations=iters)
 
 
 def emd_workspace(B, N, device):
     """The workspace houv_emd_forward needs for B clouds of N points (uint8, houv_emd_workspace_bytes), None when it needs none
     (N <= 4096)."""
-    n = _lib.load().houv_emd_workspace_bytes(int(B), int(N))
-    return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
+    return _lib.workspace("houv_emd_workspace_bytes", device, B, N, floor=0)[0]
 
 
 def emd_forward(xyz1, xyz2, eps, iters, workspace=None):
@@ -294,11 +264,7 @@ def emd_forward(xyz1, xyz2, eps, iters, workspace=None):
         need = _lib.load().houv_emd_workspace_bytes(int(B), int(N))
         if workspace.numel() * workspace.element_size() < need:
             raise _lib.HouvHipError(f"emd_forward: the workspace holds fewer than the {need} bytes needed")
-    with torch.cuda.device(dev):
-        ok = _lib.load().houv_emd_forward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, N, M, float(eps), int(iters), _lib.ptr(dist),
-                                          _lib.ptr(assignment), _lib.ptr(iters_run), _lib.ptr(workspace),
-                                          _lib.stream_of(xyz1))
-    _lib.check(ok, "houv_emd_forward")
+    _lib.call("houv_emd_forward", xyz1, xyz1, xyz2, B, N, M, eps, iters, dist, assignment, iters_run, workspace)
     return dist, assignment, iters_run
 
 
@@ -314,10 +280,7 @@ def emd_backward(xyz1, xyz2, graddist, assignment):
     if xyz2.shape != xyz1.shape or graddist.numel() != B * N or assignment.numel() != B * N:
         raise _lib.HouvHipError("emd_backward: shape mismatch")
     gradxyz1 = torch.zeros_like(xyz1)
-    with torch.cuda.device(xyz1.device):
-        ok = _lib.load().houv_emd_backward(_lib.ptr(xyz1), _lib.ptr(xyz2), B, N, _lib.ptr(graddist), _lib.ptr(assignment),
-                                           _lib.ptr(gradxyz1), _lib.stream_of(xyz1))
-    _lib.check(ok, "houv_emd_backward")
+    _lib.call("houv_emd_backward", xyz1, xyz1, xyz2, B, N, graddist, assignment, gradxyz1)
     return gradxyz1
 
 
@@ -333,44 +296,49 @@ def rri_features(xyz, idx, k, skip=0):
         raise _lib.HouvHipError("rri_features: expected xyz[B,N,3], idx[B,N,L]")
     B, N, _ = xyz.shape
     out = torch.empty((B, N, 4 * int(k)), dtype=_F32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        ok = _lib.load().houv_rri_features(_lib.ptr(xyz), _lib.ptr(idx), B, N, int(k), idx.shape[2], int(skip), _lib.ptr(out),
-                                           _lib.stream_of(xyz))
-    _lib.check(ok, "houv_rri_features")
+    _lib.call("houv_rri_features", xyz, xyz, idx, B, N, k, idx.shape[2], skip, out)
     return out
+
+
+def _gmm_params_args(who, gamma, pts, **more):
+    """(B, N, J) of gamma[B,N,J], pts[B,N,3]; `more`: the backward's further fp32 operands by name."""
+    ts = dict(gamma=gamma, pts=pts, **more)
+    _lib.require_gpu(*ts.values())
+    for n, t in ts.items():
+        _want(t, _F32, n)
+    if gamma.dim() != 3 or pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[:2] != gamma.shape[:2]:
+        raise _lib.HouvHipError(f"{who}: expected gamma[B,N,J], pts[B,N,3]")
+    return gamma.shape
+
+
+def _gmm_register_args(who, pi_s, mu_s, mu_t, sigma_t, *g_T):
+    """(B, J) of pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J] and, when the backward passes it, g_T[B,4,4]."""
+    ts = (pi_s, mu_s, mu_t, sigma_t) + g_T
+    _lib.require_gpu(*ts)
+    for t, n in zip(ts, ("pi_s", "mu_s", "mu_t", "sigma_t", "g_T")):
+        _want(t, _F32, n)
+    if pi_s.dim() != 2 or tuple(mu_s.shape) != tuple(pi_s.shape) + (3,) or mu_t.shape != mu_s.shape or sigma_t.shape != pi_s.shape \
+            or any(tuple(g.shape) != (pi_s.shape[0], 4, 4) for g in g_T):
+        raise _lib.HouvHipError(f"{who}: expected pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J]" + (", g_T[B,4,4]" if g_T else ""))
+    return pi_s.shape
 
 
 def gmm_params(gamma, pts):
     """gamma[B,N,J] (J <= 32), pts[B,N,3] -> (pi[B,J], mu[B,J,3], sigma[B,J]): deepgmr.py:98-120 with the isotropic covariance kept
     as its scalar (the reference returns sigma * eye(3))."""
-    _lib.require_gpu(gamma, pts)
-    _want(gamma, _F32, "gamma"); _want(pts, _F32, "pts")
-    if gamma.dim() != 3 or pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[:2] != gamma.shape[:2]:
-        raise _lib.HouvHipError("gmm_params: expected gamma[B,N,J], pts[B,N,3]")
-    B, N, J = gamma.shape
+    B, N, J = _gmm_params_args("gmm_params", gamma, pts)
     pi = torch.empty((B, J), dtype=_F32, device=gamma.device)
     mu = torch.empty((B, J, 3), dtype=_F32, device=gamma.device)
     sigma = torch.empty((B, J), dtype=_F32, device=gamma.device)
-    with torch.cuda.device(gamma.device):
-        ok = _lib.load().houv_gmm_params(_lib.ptr(gamma), _lib.ptr(pts), B, N, J, _lib.ptr(pi), _lib.ptr(mu), _lib.ptr(sigma),
-                                         _lib.stream_of(gamma))
-    _lib.check(ok, "houv_gmm_params")
+    _lib.call("houv_gmm_params", gamma, gamma, pts, B, N, J, pi, mu, sigma)
     return pi, mu, sigma
 
 
 def gmm_register(pi_s, mu_s, mu_t, sigma_t):
     """pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J] -> T[B,4,4], bottom row (0,0,0,1) (deepgmr.py:123-143)."""
-    _lib.require_gpu(pi_s, mu_s, mu_t, sigma_t)
-    for t, n in ((pi_s, "pi_s"), (mu_s, "mu_s"), (mu_t, "mu_t"), (sigma_t, "sigma_t")):
-        _want(t, _F32, n)
-    if pi_s.dim() != 2 or tuple(mu_s.shape) != tuple(pi_s.shape) + (3,) or mu_t.shape != mu_s.shape or sigma_t.shape != pi_s.shape:
-        raise _lib.HouvHipError("gmm_register: expected pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J]")
-    B, J = pi_s.shape
+    B, J = _gmm_register_args("gmm_register", pi_s, mu_s, mu_t, sigma_t)
     T = torch.empty((B, 4, 4), dtype=_F32, device=pi_s.device)
-    with torch.cuda.device(pi_s.device):
-        ok = _lib.load().houv_gmm_register(_lib.ptr(pi_s), _lib.ptr(mu_s), _lib.ptr(mu_t), _lib.ptr(sigma_t), B, J, _lib.ptr(T),
-                                           _lib.stream_of(pi_s))
-    _lib.check(ok, "houv_gmm_register")
+    _lib.call("houv_gmm_register", pi_s, pi_s, mu_s, mu_t, sigma_t, B, J, T)
     return T
 
 
@@ -381,38 +349,20 @@ def gmm_register(pi_s, mu_s, mu_t, sigma_t):
 def gmm_params_backward(gamma, pts, pi, mu, sigma, g_pi, g_mu, g_sigma):
     """The gradient of (pi, mu, sigma) = gmm_params(softmax(logits), pts) with respect to the logits, softmax backward
     included: gamma[B,N,J], pts[B,N,3], pi / mu / sigma as gmm_params returned them, their gradients -> g_logits[B,N,J]."""
-    ts = (gamma, pts, pi, mu, sigma, g_pi, g_mu, g_sigma)
-    _lib.require_gpu(*ts)
-    for t, n in zip(ts, ("gamma", "pts", "pi", "mu", "sigma", "g_pi", "g_mu", "g_sigma")):
-        _want(t, _F32, n)
-    if gamma.dim() != 3 or pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[:2] != gamma.shape[:2]:
-        raise _lib.HouvHipError("gmm_params_backward: expected gamma[B,N,J], pts[B,N,3]")
-    B, N, J = gamma.shape
+    B, N, J = _gmm_params_args("gmm_params_backward", gamma, pts, pi=pi, mu=mu, sigma=sigma, g_pi=g_pi, g_mu=g_mu, g_sigma=g_sigma)
     if any(tuple(t.shape) != (B, J) for t in (pi, sigma, g_pi, g_sigma)) or any(tuple(t.shape) != (B, J, 3) for t in (mu, g_mu)):
         raise _lib.HouvHipError("gmm_params_backward: expected pi / sigma and their gradients [B,J], mu / g_mu [B,J,3]")
     g_logits = torch.empty_like(gamma)
-    with torch.cuda.device(gamma.device):
-        ok = _lib.load().houv_gmm_params_backward(*[_lib.ptr(t) for t in ts], B, N, J, _lib.ptr(g_logits), _lib.stream_of(gamma))
-    _lib.check(ok, "houv_gmm_params_backward")
+    _lib.call("houv_gmm_params_backward", gamma, gamma, pts, pi, mu, sigma, g_pi, g_mu, g_sigma, B, N, J, g_logits)
     return g_logits
 
 
 def gmm_register_backward(pi_s, mu_s, mu_t, sigma_t, g_T):
     """The gradient of T = gmm_register(pi_s, mu_s, mu_t, sigma_t): g_T[B,4,4] -> (g_pi_s[B,J], g_mu_s[B,J,3], g_mu_t[B,J,3],
     g_sigma_t[B,J]); the polar form of the rotation's derivative, in float64 registers."""
-    ts = (pi_s, mu_s, mu_t, sigma_t, g_T)
-    _lib.require_gpu(*ts)
-    for t, n in zip(ts, ("pi_s", "mu_s", "mu_t", "sigma_t", "g_T")):
-        _want(t, _F32, n)
-    if pi_s.dim() != 2 or tuple(mu_s.shape) != tuple(pi_s.shape) + (3,) or mu_t.shape != mu_s.shape or sigma_t.shape != pi_s.shape \
-            or tuple(g_T.shape) != (pi_s.shape[0], 4, 4):
-        raise _lib.HouvHipError("gmm_register_backward: expected pi_s[B,J], mu_s[B,J,3], mu_t[B,J,3], sigma_t[B,J], g_T[B,4,4]")
-    B, J = pi_s.shape
+    B, J = _gmm_register_args("gmm_register_backward", pi_s, mu_s, mu_t, sigma_t, g_T)
     outs = (torch.empty_like(pi_s), torch.empty_like(mu_s), torch.empty_like(mu_t), torch.empty_like(sigma_t))
-    with torch.cuda.device(pi_s.device):
-        ok = _lib.load().houv_gmm_register_backward(*[_lib.ptr(t) for t in ts], B, J, *[_lib.ptr(t) for t in outs],
-                                                    _lib.stream_of(pi_s))
-    _lib.check(ok, "houv_gmm_register_backward")
+    _lib.call("houv_gmm_register_backward", pi_s, pi_s, mu_s, mu_t, sigma_t, g_T, B, J, *outs)
     return outs
 
 
@@ -431,22 +381,14 @@ def _bn_vectors(C, *vs):
             raise _lib.HouvHipError(f"bn_rows: expected per-channel vectors of {C} elements")
 
 
-def _bn_workspace(R, C, n_group, device):
-    nbytes = _lib.load().houv_bn_rows_workspace_bytes(R, C, n_group)
-    return torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=device), nbytes
-
-
 def bn_rows_stats(z):
     """z[R,C] (R >= 2, any row stride) -> (mean[C], var[C]): the batch statistics of training-mode BatchNorm, var biased about
     the mean.  Ordered sums: the same bits from call to call."""
     R, C, ld = _bn_rows(z, "bn_rows_stats")
     mean = torch.empty((C,), dtype=_F32, device=z.device)
     var = torch.empty((C,), dtype=_F32, device=z.device)
-    ws, nbytes = _bn_workspace(R, C, 0, z.device)
-    with torch.cuda.device(z.device):
-        ok = _lib.load().houv_bn_rows_stats(ctypes_ptr(z), R, C, ld, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(ws), nbytes,
-                                            _lib.stream_of(z))
-    _lib.check(ok, "houv_bn_rows_stats")
+    ws, nbytes = _lib.workspace("houv_bn_rows_workspace_bytes", z.device, R, C, 0)
+    _lib.call("houv_bn_rows_stats", z, z, R, C, ld, mean, var, ws, nbytes)
     return mean, var
 
 
@@ -464,12 +406,8 @@ def bn_relu_rows(z, mean, var, weight, bias, eps=1e-5, relu=True, n_group=0):
     if n_group:
         gmax = torch.empty((R // n_group, C), dtype=_F32, device=z.device)
         garg = torch.empty((R // n_group, C), dtype=_I32, device=z.device)
-    ws, nbytes = _bn_workspace(R, C, n_group, z.device)
-    with torch.cuda.device(z.device):
-        ok = _lib.load().houv_bn_relu_rows(ctypes_ptr(z), R, C, ld, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(weight), _lib.ptr(bias),
-                                           float(eps), int(bool(relu)), n_group, _lib.ptr(y), C, _lib.ptr(gmax), _lib.ptr(garg),
-                                           _lib.ptr(ws), nbytes, _lib.stream_of(z))
-    _lib.check(ok, "houv_bn_relu_rows")
+    ws, nbytes = _lib.workspace("houv_bn_rows_workspace_bytes", z.device, R, C, n_group)
+    _lib.call("houv_bn_relu_rows", z, z, R, C, ld, mean, var, weight, bias, eps, bool(relu), n_group, y, C, gmax, garg, ws, nbytes)
     return (y, gmax, garg) if n_group else y
 
 
@@ -484,13 +422,9 @@ def bn_relu_rows_backward(gy, z, mean, var, weight, bias, eps=1e-5, relu=True, i
     gz = gy if inplace else torch.empty((R, C), dtype=_F32, device=z.device)
     gweight = torch.empty((C,), dtype=_F32, device=z.device)
     gbias = torch.empty((C,), dtype=_F32, device=z.device)
-    ws, nbytes = _bn_workspace(R, C, 0, z.device)
-    with torch.cuda.device(z.device):
-        ok = _lib.load().houv_bn_relu_rows_backward(ctypes_ptr(gy), ldg, ctypes_ptr(z), R, C, ld, _lib.ptr(mean), _lib.ptr(var),
-                                                    _lib.ptr(weight), _lib.ptr(bias), float(eps), int(bool(relu)), ctypes_ptr(gz),
-                                                    gz.stride(0), _lib.ptr(gweight), _lib.ptr(gbias), _lib.ptr(ws), nbytes,
-                                                    _lib.stream_of(z))
-    _lib.check(ok, "houv_bn_relu_rows_backward")
+    ws, nbytes = _lib.workspace("houv_bn_rows_workspace_bytes", z.device, R, C, 0)
+    _lib.call("houv_bn_relu_rows_backward", z, gy, ldg, z, R, C, ld, mean, var, weight, bias, eps, bool(relu), gz, gz.stride(0),
+              gweight, gbias, ws, nbytes)
     return gz, gweight, gbias
 
 
@@ -520,11 +454,7 @@ def idam_simmat(src, tgt, es, et, W1, s1, t1, W2, b2, W3, s3, t3, w4, b4, want_r
     cidx = torch.empty((B, Ms), dtype=_I32, device=dev) if want_idx else None
     corr = torch.empty((B, 3, Ms), dtype=_F32, device=dev) if want_corr else None
     scores = torch.empty((B, Ms, Mt), dtype=_F32, device=dev) if want_scores else None
-    with torch.cuda.device(dev):
-        ok = _lib.load().houv_idam_simmat(_lib.ptr(src), _lib.ptr(tgt), _lib.ptr(es), _lib.ptr(et), B, Ms, Mt, E,
-                                          *[_lib.ptr(t) for t in par], _lib.ptr(rowmax), _lib.ptr(cidx), _lib.ptr(corr),
-                                          _lib.ptr(scores), _lib.stream_of(src))
-    _lib.check(ok, "houv_idam_simmat")
+    _lib.call("houv_idam_simmat", src, src, tgt, es, et, B, Ms, Mt, E, *par, rowmax, cidx, corr, scores)
     return rowmax, cidx, corr, scores
 
 
@@ -540,10 +470,7 @@ def edge_diff(x, idx, k=None, ldo=None):
     k = idx.shape[2] if k is None else int(k)
     ldo = C if ldo is None else int(ldo)
     out = torch.empty((B * N * k, ldo), dtype=_F32, device=x.device)
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_edge_diff(_lib.ptr(x), _lib.ptr(idx), B, N, k, C, idx.shape[2], ldo, _lib.ptr(out),
-                                        _lib.stream_of(x))
-    _lib.check(ok, "houv_edge_diff")
+    _lib.call("houv_edge_diff", x, x, idx, B, N, k, C, idx.shape[2], ldo, out)
     return out
 
 
@@ -553,35 +480,41 @@ def edge_diff(x, idx, k=None, ldo=None):
 PCN_ROW_TILE = 64      # HOUV_PCN_ROW_TILE: points per workgroup of both kernels (a partial tile begins at its multiples)
 
 
+def _mlp2_dims(who, x, W1, W2, *b2):
+    """(B, N, Cin, H, Cout) of a PointNet block's x[B,N,Cin], W1[H,Cin], W2[Cout,H]; the forward passes its b2[Cout] as well."""
+    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0] \
+            or any(b.numel() != W2.shape[0] for b in b2):
+        raise _lib.HouvHipError(f"{who}: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H]{', b2[Cout]' if b2 else ''}, got "
+                                + ", ".join(str(tuple(t.shape)) for t in (x, W1, W2) + b2))
+    return x.shape[0], x.shape[1], x.shape[2], W1.shape[0], W2.shape[0]
+
+
+def _shift1_stride(who, shift1, B, H):
+    """The row stride the entries are told for shift1: 0 for one bias [H] shared by all clouds, H for one row per cloud [B,H]."""
+    if tuple(shift1.shape) not in ((H,), (B, H)):
+        raise _lib.HouvHipError(f"{who}: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    return 0 if shift1.dim() == 1 else H
+
+
+def _mlp2_forward_args(who, x, W1, shift1, W2, b2):
+    """(B, N, Cin, H, Cout, shift1's row stride) of mlp2_max's and mlp2_max_arg's operands."""
+    _lib.require_gpu(x, W1, shift1, W2, b2)
+    for t, n in ((x, "x"), (W1, "W1"), (shift1, "shift1"), (W2, "W2"), (b2, "b2")):
+        _want(t, _F32, f"{who}: {n}")
+    B, N, Cin, H, Cout = _mlp2_dims(who, x, W1, W2, b2)
+    return B, N, Cin, H, Cout, _shift1_stride(who, shift1, B, H)
+
+
 def mlp2_max(x, W1, shift1, W2, b2, want_y=False):
     """One PointNet block in one kernel (houv_mlp2_max): x[B,N,Cin], W1[H,Cin], shift1[H] (one bias for all clouds) or [B,H]
     (one row per cloud), W2[Cout,H], b2[Cout] -> (pooled[B,Cout], y[B,N,Cout] or None) with
     y = W2 . relu(W1 . x + shift1) + b2 and pooled = y.max(1).  (Cin, H, Cout) = (3, 128, 256) or (256, 512, 1024)."""
-    _lib.require_gpu(x, W1, shift1, W2, b2)
-    for t, n in ((x, "x"), (W1, "W1"), (shift1, "shift1"), (W2, "W2"), (b2, "b2")):
-        _want(t, _F32, f"mlp2_max: {n}")
-    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0] \
-            or b2.numel() != W2.shape[0]:
-        raise _lib.HouvHipError(f"mlp2_max: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H], b2[Cout], got {tuple(x.shape)}, "
-                                f"{tuple(W1.shape)}, {tuple(W2.shape)}, {tuple(b2.shape)}")
-    B, N, Cin = x.shape
-    H, Cout = W1.shape[0], W2.shape[0]
-    if tuple(shift1.shape) == (H,):
-        stride = 0
-    elif tuple(shift1.shape) == (B, H):
-        stride = H
-    else:
-        raise _lib.HouvHipError(f"mlp2_max: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    B, N, Cin, H, Cout, stride = _mlp2_forward_args("mlp2_max", x, W1, shift1, W2, b2)
     dev = x.device
     pooled = torch.empty((B, Cout), dtype=_F32, device=dev)
     y = torch.empty((B, N, Cout), dtype=_F32, device=dev) if want_y else None
-    lib = _lib.load()
-    nbytes = lib.houv_mlp2_max_workspace_bytes(B, N, Cout)
-    ws = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes > 0 else None
-    with torch.cuda.device(dev):
-        ok = lib.houv_mlp2_max(_lib.ptr(x), B, N, Cin, _lib.ptr(W1), H, _lib.ptr(shift1), stride, _lib.ptr(W2), _lib.ptr(b2),
-                               Cout, _lib.ptr(pooled), _lib.ptr(y), _lib.ptr(ws), _lib.stream_of(x))
-    _lib.check(ok, "houv_mlp2_max")
+    ws = _lib.workspace("houv_mlp2_max_workspace_bytes", dev, B, N, Cout, floor=0)[0]
+    _lib.call("houv_mlp2_max", x, x, B, N, Cin, W1, H, shift1, stride, W2, b2, Cout, pooled, y, ws)
     return pooled, y
 
 
@@ -589,32 +522,13 @@ def mlp2_max_arg(x, W1, shift1, W2, b2, want_y=False):
     """mlp2_max that also says where each maximum sits (houv_mlp2_max_arg): the same arguments ->
     (pooled[B,Cout], arg[B,Cout] int32, y or None).  pooled and y carry mlp2_max's bits; arg[b,c] is the lowest n with
     y[b,n,c] == pooled[b,c] (torch.max's rule on the CPU), -1 for a column that is NaN in every row."""
-    _lib.require_gpu(x, W1, shift1, W2, b2)
-    for t, n in ((x, "x"), (W1, "W1"), (shift1, "shift1"), (W2, "W2"), (b2, "b2")):
-        _want(t, _F32, f"mlp2_max_arg: {n}")
-    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0] \
-            or b2.numel() != W2.shape[0]:
-        raise _lib.HouvHipError(f"mlp2_max_arg: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H], b2[Cout], got {tuple(x.shape)}, "
-                                f"{tuple(W1.shape)}, {tuple(W2.shape)}, {tuple(b2.shape)}")
-    B, N, Cin = x.shape
-    H, Cout = W1.shape[0], W2.shape[0]
-    if tuple(shift1.shape) == (H,):
-        stride = 0
-    elif tuple(shift1.shape) == (B, H):
-        stride = H
-    else:
-        raise _lib.HouvHipError(f"mlp2_max_arg: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    B, N, Cin, H, Cout, stride = _mlp2_forward_args("mlp2_max_arg", x, W1, shift1, W2, b2)
     dev = x.device
     pooled = torch.empty((B, Cout), dtype=_F32, device=dev)
     arg = torch.empty((B, Cout), dtype=_I32, device=dev)
     y = torch.empty((B, N, Cout), dtype=_F32, device=dev) if want_y else None
-    lib = _lib.load()
-    nbytes = lib.houv_mlp2_max_arg_workspace_bytes(B, N, Cout)
-    ws = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes > 0 else None
-    with torch.cuda.device(dev):
-        ok = lib.houv_mlp2_max_arg(_lib.ptr(x), B, N, Cin, _lib.ptr(W1), H, _lib.ptr(shift1), stride, _lib.ptr(W2), _lib.ptr(b2),
-                                   Cout, _lib.ptr(pooled), _lib.ptr(arg), _lib.ptr(y), _lib.ptr(ws), _lib.stream_of(x))
-    _lib.check(ok, "houv_mlp2_max_arg")
+    ws = _lib.workspace("houv_mlp2_max_arg_workspace_bytes", dev, B, N, Cout, floor=0)[0]
+    _lib.call("houv_mlp2_max_arg", x, x, B, N, Cin, W1, H, shift1, stride, W2, b2, Cout, pooled, arg, y, ws)
     return pooled, arg, y
 
 
@@ -630,19 +544,10 @@ def mlp2_max_backward(x, W1, shift1, W2, arg, gpooled, rows=None, nrows=None, gy
     for t, n in zip(ts, ("x", "W1", "shift1", "W2", "gpooled")):
         _want(t, _F32, f"mlp2_max_backward: {n}")
     _want(arg, _I32, "mlp2_max_backward: arg")
-    if x.dim() != 3 or W1.dim() != 2 or W2.dim() != 2 or W1.shape[1] != x.shape[2] or W2.shape[1] != W1.shape[0]:
-        raise _lib.HouvHipError(f"mlp2_max_backward: expected x[B,N,Cin], W1[H,Cin], W2[Cout,H], got {tuple(x.shape)}, "
-                                f"{tuple(W1.shape)}, {tuple(W2.shape)}")
-    B, N, Cin = x.shape
-    H, Cout = W1.shape[0], W2.shape[0]
+    B, N, Cin, H, Cout = _mlp2_dims("mlp2_max_backward", x, W1, W2)
     if tuple(arg.shape) != (B, Cout) or tuple(gpooled.shape) != (B, Cout):
         raise _lib.HouvHipError(f"mlp2_max_backward: arg and gpooled must be [{B},{Cout}], got {tuple(arg.shape)}, {tuple(gpooled.shape)}")
-    if tuple(shift1.shape) == (H,):
-        stride = 0
-    elif tuple(shift1.shape) == (B, H):
-        stride = H
-    else:
-        raise _lib.HouvHipError(f"mlp2_max_backward: shift1 must be [{H}] or [{B},{H}], got {tuple(shift1.shape)}")
+    stride = _shift1_stride("mlp2_max_backward", shift1, B, H)
     R = 0
     if rows is not None or nrows is not None or gy_rows is not None:
         if rows is None or nrows is None or gy_rows is None:
@@ -657,77 +562,54 @@ def mlp2_max_backward(x, W1, shift1, W2, arg, gpooled, rows=None, nrows=None, gy
         if R == 0:
             rows = nrows = gy_rows = None
     dev = x.device
-    lib = _lib.load()
-    rcap = lib.houv_mlp2_max_backward_rows(N, Cout, R)
+    rcap = _lib.load().houv_mlp2_max_backward_rows(N, Cout, R)
     out = dict(gW1=torch.empty((H, Cin), dtype=_F32, device=dev), gshift1=torch.empty((B, H), dtype=_F32, device=dev),
                gW2=torch.empty((Cout, H), dtype=_F32, device=dev), gb2=torch.empty((Cout,), dtype=_F32, device=dev),
                act_rows=torch.empty((B, rcap), dtype=_I32, device=dev), nact=torch.empty((B,), dtype=_I32, device=dev),
                gx_rows=torch.empty((B, rcap, Cin), dtype=_F32, device=dev) if want_gx else None)
-    nbytes = lib.houv_mlp2_max_backward_workspace_bytes(B, N, Cin, H, Cout, R)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
-    with torch.cuda.device(dev):
-        ok = lib.houv_mlp2_max_backward(_lib.ptr(x), B, N, Cin, _lib.ptr(W1), H, _lib.ptr(shift1), stride, _lib.ptr(W2), Cout,
-                                        _lib.ptr(arg), _lib.ptr(gpooled), _lib.ptr(rows), _lib.ptr(nrows), _lib.ptr(gy_rows), R,
-                                        _lib.ptr(out["gW1"]), _lib.ptr(out["gshift1"]), _lib.ptr(out["gW2"]), _lib.ptr(out["gb2"]),
-                                        _lib.ptr(out["act_rows"]), _lib.ptr(out["nact"]), _lib.ptr(out["gx_rows"]), _lib.ptr(ws),
-                                        _lib.stream_of(x))
-    _lib.check(ok, "houv_mlp2_max_backward")
+    ws = _lib.workspace("houv_mlp2_max_backward_workspace_bytes", dev, B, N, Cin, H, Cout, R)[0]
+    _lib.call("houv_mlp2_max_backward", x, x, B, N, Cin, W1, H, shift1, stride, W2, Cout, arg, gpooled, rows, nrows, gy_rows, R,
+              *out.values(), ws)      # out: gW1, gshift1, gW2, gb2, act_rows, nact, gx_rows, the entry's order
     return out
+
+
+def _pcn_fold_args(who, coarse, cvec, grid, Wgp, W2, b2, W3, b3, *gfine):
+    """(B, nc, scale) of pcn_fold's operands; `gfine`: the backward's further fp32 operand (its shape is the backward's to check)."""
+    ts = (coarse, cvec, grid, Wgp, W2, b2, W3, b3) + gfine
+    _lib.require_gpu(*ts)
+    for t in ts:
+        _want(t, _F32, who)
+    if coarse.dim() != 3 or coarse.shape[2] != 3 or grid.dim() != 2 or grid.shape[0] != 2 \
+            or tuple(cvec.shape) != (coarse.shape[0], 512):
+        raise _lib.HouvHipError(f"{who}: expected coarse[B,nc,3], cvec[B,512], grid[2,scale], got {tuple(coarse.shape)}, "
+                                f"{tuple(cvec.shape)}, {tuple(grid.shape)}")
+    if tuple(Wgp.shape) != (512, 5) or tuple(W2.shape) != (512, 512) or b2.numel() != 512 or tuple(W3.shape) != (3, 512) \
+            or b3.numel() != 3:
+        raise _lib.HouvHipError(f"{who}: expected Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3]")
+    return coarse.shape[0], coarse.shape[1], grid.shape[1]
 
 
 def pcn_fold(coarse, cvec, grid, Wgp, W2, b2, W3, b3):
     """The folding stage of PCN_decoder.forward (registration/models/pcn.py:108-125) in one kernel (houv_pcn_fold):
     coarse[B,nc,3], cvec[B,512], grid[2,scale], Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3] -> fine[B,nc*scale,3]."""
-    ts = (coarse, cvec, grid, Wgp, W2, b2, W3, b3)
-    _lib.require_gpu(*ts)
-    for t in ts:
-        _want(t, _F32, "pcn_fold")
-    if coarse.dim() != 3 or coarse.shape[2] != 3 or grid.dim() != 2 or grid.shape[0] != 2 \
-            or tuple(cvec.shape) != (coarse.shape[0], 512):
-        raise _lib.HouvHipError(f"pcn_fold: expected coarse[B,nc,3], cvec[B,512], grid[2,scale], got {tuple(coarse.shape)}, "
-                                f"{tuple(cvec.shape)}, {tuple(grid.shape)}")
-    if tuple(Wgp.shape) != (512, 5) or tuple(W2.shape) != (512, 512) or b2.numel() != 512 or tuple(W3.shape) != (3, 512) \
-            or b3.numel() != 3:
-        raise _lib.HouvHipError("pcn_fold: expected Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3]")
-    B, nc, _ = coarse.shape
-    scale = grid.shape[1]
+    B, nc, scale = _pcn_fold_args("pcn_fold", coarse, cvec, grid, Wgp, W2, b2, W3, b3)
     fine = torch.empty((B, nc * scale, 3), dtype=_F32, device=coarse.device)
-    with torch.cuda.device(coarse.device):
-        ok = _lib.load().houv_pcn_fold(_lib.ptr(coarse), _lib.ptr(cvec), _lib.ptr(grid), B, nc, scale, _lib.ptr(Wgp), _lib.ptr(W2),
-                                       _lib.ptr(b2), _lib.ptr(W3), _lib.ptr(b3), _lib.ptr(fine), _lib.stream_of(coarse))
-    _lib.check(ok, "houv_pcn_fold")
+    _lib.call("houv_pcn_fold", coarse, coarse, cvec, grid, B, nc, scale, Wgp, W2, b2, W3, b3, fine)
     return fine
 
 
 def pcn_fold_backward(coarse, cvec, grid, Wgp, W2, b2, W3, b3, gfine):
     """The backward pass of pcn_fold (houv_pcn_fold_backward): pcn_fold's arguments plus
     gfine[B,nc*scale,3] -> dict(gcoarse[B,nc,3], gcvec[B,512], gWgp[512,5], gW2[512,512], gb2[512], gW3[3,512], gb3[3])."""
-    ts = (coarse, cvec, grid, Wgp, W2, b2, W3, b3, gfine)
-    _lib.require_gpu(*ts)
-    for t in ts:
-        _want(t, _F32, "pcn_fold_backward")
-    if coarse.dim() != 3 or coarse.shape[2] != 3 or grid.dim() != 2 or grid.shape[0] != 2 \
-            or tuple(cvec.shape) != (coarse.shape[0], 512):
-        raise _lib.HouvHipError(f"pcn_fold_backward: expected coarse[B,nc,3], cvec[B,512], grid[2,scale], got {tuple(coarse.shape)}, "
-                                f"{tuple(cvec.shape)}, {tuple(grid.shape)}")
-    if tuple(Wgp.shape) != (512, 5) or tuple(W2.shape) != (512, 512) or b2.numel() != 512 or tuple(W3.shape) != (3, 512) \
-            or b3.numel() != 3:
-        raise _lib.HouvHipError("pcn_fold_backward: expected Wgp[512,5], W2[512,512], b2[512], W3[3,512], b3[3]")
-    B, nc, _ = coarse.shape
-    scale = grid.shape[1]
+    B, nc, scale = _pcn_fold_args("pcn_fold_backward", coarse, cvec, grid, Wgp, W2, b2, W3, b3, gfine)
     if tuple(gfine.shape) != (B, nc * scale, 3):
         raise _lib.HouvHipError(f"pcn_fold_backward: gfine must be [{B},{nc * scale},3], got {tuple(gfine.shape)}")
     dev = coarse.device
     new = lambda *shape: torch.empty(shape, dtype=_F32, device=dev)
     out = dict(gcoarse=new(B, nc, 3), gcvec=new(B, 512), gWgp=new(512, 5), gW2=new(512, 512), gb2=new(512), gW3=new(3, 512), gb3=new(3))
-    lib = _lib.load()
-    nbytes = lib.houv_pcn_fold_backward_workspace_bytes(B, nc, scale)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
-    with torch.cuda.device(dev):
-        ok = lib.houv_pcn_fold_backward(*(_lib.ptr(t) for t in ts[:3]), B, nc, scale, *(_lib.ptr(t) for t in ts[3:]),
-                                        *(_lib.ptr(out[k]) for k in ("gcoarse", "gcvec", "gWgp", "gW2", "gb2", "gW3", "gb3")),
-                                        _lib.ptr(ws), nbytes, _lib.stream_of(coarse))
-    _lib.check(ok, "houv_pcn_fold_backward")
+    ws, nbytes = _lib.workspace("houv_pcn_fold_backward_workspace_bytes", dev, B, nc, scale)
+    _lib.call("houv_pcn_fold_backward", coarse, coarse, cvec, grid, B, nc, scale, Wgp, W2, b2, W3, b3, gfine,
+              *(out[k] for k in ("gcoarse", "gcvec", "gWgp", "gW2", "gb2", "gW3", "gb3")), ws, nbytes)
     return out
 
 
@@ -755,10 +637,18 @@ def knn_feat(x, k, want_dist=False):
     B, N, C, ldx = _rows(x, "knn_feat: x")
     idx = torch.empty((B, N, int(k)), dtype=_I32, device=x.device)
     d2 = torch.empty((B, N, int(k)), dtype=_F32, device=x.device) if want_dist else None
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_knn_feat(ctypes_ptr(x), B, N, C, ldx, int(k), _lib.ptr(idx), _lib.ptr(d2), _lib.stream_of(x))
-    _lib.check(ok, "houv_knn_feat")
+    _lib.call("houv_knn_feat", x, x, B, N, C, ldx, k, idx, d2)
     return (idx, d2) if want_dist else idx
+
+
+def _out_rows(who, name, out, shape, device):
+    """(out, its row stride): the caller's `out`, or a dense fp32 one allocated here, of exactly `shape` and laid out as _rows
+    asks.  The caller has taken a given `out` through require_gpu_any."""
+    if out is None:
+        out = torch.empty(shape, dtype=_F32, device=device)
+    if tuple(out.shape) != shape:
+        raise _lib.HouvHipError(f"{who}: {name} must be [{','.join(map(str, shape))}], got {tuple(out.shape)}")
+    return out, _rows(out, f"{who}: {name}")[3]
 
 
 def dense_conv(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
@@ -766,31 +656,15 @@ def dense_conv(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
     rows (C = 24 or 48), idx[B,N,k] int32 neighbour lists, W0[24,2C], W1[24,24+C], W2[24,48+C], biases [24] ->
     out[B,N,C+72] = max over the neighbours of cat(y0, x_i, s1, s2), relu applied when relu_out.  `out` may be a [B,N,C+72]
     column slice of a wider row-major buffer (the caller's cat(dense, x)); its other columns are left alone."""
-    _lib.require_gpu_any(x, W0, b0, W1, b1, W2, b2, out)
-    _lib.require_gpu(idx, W0, b0, W1, b1, W2, b2); _want(idx, _I32, "dense_conv: idx")
-    B, N, C, ldx = _rows(x, "dense_conv: x")
-    G = DENSE_CONV_GROWTH
-    if idx.dim() != 3 or tuple(idx.shape[:2]) != (B, N):
-        raise _lib.HouvHipError(f"dense_conv: expected idx[{B},{N},k], got {tuple(idx.shape)}")
-    if tuple(W0.shape) != (G, 2 * C) or tuple(W1.shape) != (G, G + C) or tuple(W2.shape) != (G, 2 * G + C) \
-            or b0.numel() != G or b1.numel() != G or b2.numel() != G:
-        raise _lib.HouvHipError(f"dense_conv: expected W0[24,{2 * C}], W1[24,{G + C}], W2[24,{2 * G + C}] and biases [24], got "
-                                f"{tuple(W0.shape)}, {tuple(W1.shape)}, {tuple(W2.shape)}")
-    if out is None:
-        out = torch.empty((B, N, C + 3 * G), dtype=_F32, device=x.device)
-    if tuple(out.shape) != (B, N, C + 3 * G):
-        raise _lib.HouvHipError(f"dense_conv: out must be [{B},{N},{C + 3 * G}], got {tuple(out.shape)}")
-    ldo = _rows(out, "dense_conv: out")[3]
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_dense_conv(ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, idx.shape[2], _lib.ptr(W0), _lib.ptr(b0),
-                                         _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), int(bool(relu_out)),
-                                         ctypes_ptr(out), ldo, _lib.stream_of(x))
-    _lib.check(ok, "houv_dense_conv")
+    B, N, C, ldx = _dense_conv_args("dense_conv", x, idx, W0, b0, W1, b1, W2, b2, out)
+    out, ldo = _out_rows("dense_conv", "out", out, (B, N, C + 3 * DENSE_CONV_GROWTH), x.device)
+    _lib.call("houv_dense_conv", x, x, ldx, idx, B, N, C, idx.shape[2], W0, b0, W1, b1, W2, b2, bool(relu_out), out, ldo)
     return out
 
 
-def _dense_conv_args(who, x, idx, W0, b0, W1, b1, W2, b2):
-    _lib.require_gpu_any(x, W0, b0, W1, b1, W2, b2)
+def _dense_conv_args(who, x, idx, W0, b0, W1, b1, W2, b2, out=None):
+    """(B, N, C, x's row stride) of dense_conv's operands; `out`: an output to take through the first check with them."""
+    _lib.require_gpu_any(x, W0, b0, W1, b1, W2, b2, out)
     _lib.require_gpu(idx, W0, b0, W1, b1, W2, b2); _want(idx, _I32, f"{who}: idx")
     B, N, C, ldx = _rows(x, f"{who}: x")
     G = DENSE_CONV_GROWTH
@@ -810,18 +684,10 @@ def dense_conv_arg(x, idx, W0, b0, W1, b1, W2, b2, relu_out=False, out=None):
     neighbour."""
     B, N, C, ldx = _dense_conv_args("dense_conv_arg", x, idx, W0, b0, W1, b1, W2, b2)
     G = DENSE_CONV_GROWTH
-    if out is None:
-        out = torch.empty((B, N, C + 3 * G), dtype=_F32, device=x.device)
     _lib.require_gpu_any(x, out)
-    if tuple(out.shape) != (B, N, C + 3 * G):
-        raise _lib.HouvHipError(f"dense_conv_arg: out must be [{B},{N},{C + 3 * G}], got {tuple(out.shape)}")
-    ldo = _rows(out, "dense_conv_arg: out")[3]
+    out, ldo = _out_rows("dense_conv_arg", "out", out, (B, N, C + 3 * G), x.device)
     arg = torch.empty((B, N, 3 * G), dtype=torch.int8, device=x.device)
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_dense_conv_arg(ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, idx.shape[2], _lib.ptr(W0), _lib.ptr(b0),
-                                             _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), int(bool(relu_out)),
-                                             ctypes_ptr(out), ldo, _lib.ptr(arg), _lib.stream_of(x))
-    _lib.check(ok, "houv_dense_conv_arg")
+    _lib.call("houv_dense_conv_arg", x, x, ldx, idx, B, N, C, idx.shape[2], W0, b0, W1, b1, W2, b2, bool(relu_out), out, ldo, arg)
     return out, arg
 
 
@@ -847,24 +713,13 @@ def dense_conv_backward(x, idx, W0, b0, W1, b1, W2, b2, arg, gout, out=None, rel
     else:
         out = None
     dev = x.device
-    if gx is None:
-        gx = torch.empty((B, N, C), dtype=_F32, device=dev)
-    if tuple(gx.shape) != (B, N, C):
-        raise _lib.HouvHipError(f"dense_conv_backward: gx must be [{B},{N},{C}], got {tuple(gx.shape)}")
-    ldgx = _rows(gx, "dense_conv_backward: gx")[3]
+    gx, ldgx = _out_rows("dense_conv_backward", "gx", gx, (B, N, C), dev)
     new = lambda *shape: torch.empty(shape, dtype=_F32, device=dev)
     res = dict(gx=gx, gW0=new(G, 2 * C), gb0=new(G), gW1=new(G, G + C), gb1=new(G), gW2=new(G, 2 * G + C), gb2=new(G))
-    lib = _lib.load()
     k = idx.shape[2]
-    nbytes = lib.houv_dense_conv_backward_workspace_bytes(B, N, C, k)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
-    with torch.cuda.device(dev):
-        ok = lib.houv_dense_conv_backward(ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, k, _lib.ptr(W0), _lib.ptr(b0), _lib.ptr(W1),
-                                          _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), int(bool(relu_out)), _lib.ptr(arg),
-                                          ctypes_ptr(out) if out is not None else None, ldo, ctypes_ptr(gout), ldg,
-                                          ctypes_ptr(gx), ldgx, *(_lib.ptr(res[n]) for n in ("gW0", "gb0", "gW1", "gb1", "gW2", "gb2")),
-                                          _lib.ptr(ws), nbytes, _lib.stream_of(x))
-    _lib.check(ok, "houv_dense_conv_backward")
+    ws, nbytes = _lib.workspace("houv_dense_conv_backward_workspace_bytes", dev, B, N, C, k)
+    _lib.call("houv_dense_conv_backward", x, x, ldx, idx, B, N, C, k, W0, b0, W1, b1, W2, b2, bool(relu_out), arg, out, ldo, gout, ldg,
+              gx, ldgx, *(res[n] for n in ("gW0", "gb0", "gW1", "gb1", "gW2", "gb2")), ws, nbytes)
     return res
 
 
@@ -896,16 +751,8 @@ def sa_attn(P, x, idx, Ww1, Ww2, bw2, Wout, bout, relu_out=False, out=None):
         raise _lib.HouvHipError(f"sa_attn: expected Ww1[{m},{rel * (k + 1)}], Ww2[{k * m},{m}], bw2[{k * m}], Wout[{C},{mid}], "
                                 f"bout[{C}], got {tuple(Ww1.shape)}, {tuple(Ww2.shape)}, {tuple(bw2.shape)}, {tuple(Wout.shape)}, "
                                 f"{tuple(bout.shape)}")
-    if out is None:
-        out = torch.empty((B, N, C), dtype=_F32, device=x.device)
-    if tuple(out.shape) != (B, N, C):
-        raise _lib.HouvHipError(f"sa_attn: out must be [{B},{N},{C}], got {tuple(out.shape)}")
-    ldo = _rows(out, "sa_attn: out")[3]
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_sa_attn(ctypes_ptr(P), ldp, ctypes_ptr(x), ldx, _lib.ptr(idx), B, N, C, k, _lib.ptr(Ww1),
-                                      _lib.ptr(Ww2), _lib.ptr(bw2), _lib.ptr(Wout), _lib.ptr(bout), int(bool(relu_out)),
-                                      ctypes_ptr(out), ldo, _lib.stream_of(x))
-    _lib.check(ok, "houv_sa_attn")
+    out, ldo = _out_rows("sa_attn", "out", out, (B, N, C), x.device)
+    _lib.call("houv_sa_attn", x, P, ldp, x, ldx, idx, B, N, C, k, Ww1, Ww2, bw2, Wout, bout, bool(relu_out), out, ldo)
     return out
 
 
@@ -933,20 +780,11 @@ def sa_attn_backward(P, idx, Ww1, Ww2, bw2, G, gP=None):
     ldg = _rows(G, "sa_attn_backward: G")[3]
     dev = P.device
     new = lambda *shape: torch.empty(shape, dtype=_F32, device=dev)
-    if gP is None:
-        gP = new(B, N, wp)
-    if tuple(gP.shape) != (B, N, wp):
-        raise _lib.HouvHipError(f"sa_attn_backward: gP must be [{B},{N},{wp}], got {tuple(gP.shape)}")
-    ldgp = _rows(gP, "sa_attn_backward: gP")[3]
+    gP, ldgp = _out_rows("sa_attn_backward", "gP", gP, (B, N, wp), dev)
     res = dict(gP=gP, ro=new(B, N, mid), gWw1=new(m, rel * (k + 1)), gWw2=new(k * m, m), gbw2=new(k * m))
-    lib = _lib.load()
-    nbytes = lib.houv_sa_attn_backward_workspace_bytes(B, N, C, k)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=_F32, device=dev)
-    with torch.cuda.device(dev):
-        ok = lib.houv_sa_attn_backward(ctypes_ptr(P), ldp, _lib.ptr(idx), B, N, C, k, _lib.ptr(Ww1), _lib.ptr(Ww2), _lib.ptr(bw2),
-                                       ctypes_ptr(G), ldg, ctypes_ptr(gP), ldgp, _lib.ptr(res["ro"]), mid, _lib.ptr(res["gWw1"]),
-                                       _lib.ptr(res["gWw2"]), _lib.ptr(res["gbw2"]), _lib.ptr(ws), nbytes, _lib.stream_of(P))
-    _lib.check(ok, "houv_sa_attn_backward")
+    ws, nbytes = _lib.workspace("houv_sa_attn_backward_workspace_bytes", dev, B, N, C, k)
+    _lib.call("houv_sa_attn_backward", P, P, ldp, idx, B, N, C, k, Ww1, Ww2, bw2, G, ldg, gP, ldgp, res["ro"], mid, res["gWw1"],
+              res["gWw2"], res["gbw2"], ws, nbytes)
     return res
 
 
@@ -965,16 +803,9 @@ def edge_pool(feat, p_idx, pn_idx, out=None, want_arg=False):
     _lib.require_gpu_any(feat, out)
     B, N, C, ldx = _rows(feat, "edge_pool: feat")
     S, pk = _edge_pool_lists("edge_pool", p_idx, pn_idx, B)
-    if out is None:
-        out = torch.empty((B, S, 2 * C), dtype=_F32, device=feat.device)
-    if tuple(out.shape) != (B, S, 2 * C):
-        raise _lib.HouvHipError(f"edge_pool: out must be [{B},{S},{2 * C}], got {tuple(out.shape)}")
-    ldo = _rows(out, "edge_pool: out")[3]
+    out, ldo = _out_rows("edge_pool", "out", out, (B, S, 2 * C), feat.device)
     arg = torch.empty((B, S, C), dtype=torch.int8, device=feat.device) if want_arg else None
-    with torch.cuda.device(feat.device):
-        ok = _lib.load().houv_edge_pool(ctypes_ptr(feat), ldx, _lib.ptr(p_idx), _lib.ptr(pn_idx), B, N, S, C, pk, ctypes_ptr(out), ldo,
-                                        _lib.ptr(arg), _lib.stream_of(feat))
-    _lib.check(ok, "houv_edge_pool")
+    _lib.call("houv_edge_pool", feat, feat, ldx, p_idx, pn_idx, B, N, S, C, pk, out, ldo, arg)
     return (out, arg) if want_arg else out
 
 
@@ -993,13 +824,8 @@ def edge_pool_backward(g, p_idx, pn_idx, arg, N):
                                 f"{arg.dtype} {tuple(arg.shape)}")
     dev = g.device
     gfeat = torch.empty((B, int(N), C), dtype=_F32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.houv_edge_pool_backward_workspace_bytes(B, int(N), S, pk)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=dev)
-    with torch.cuda.device(dev):
-        ok = lib.houv_edge_pool_backward(ctypes_ptr(g), ldg, _lib.ptr(p_idx), _lib.ptr(pn_idx), _lib.ptr(arg), B, int(N), S, C, pk,
-                                         _lib.ptr(gfeat), C, _lib.ptr(ws), nbytes, _lib.stream_of(g))
-    _lib.check(ok, "houv_edge_pool_backward")
+    ws, nbytes = _lib.workspace("houv_edge_pool_backward_workspace_bytes", dev, B, N, S, pk)
+    _lib.call("houv_edge_pool_backward", g, g, ldg, p_idx, pn_idx, arg, B, N, S, C, pk, gfeat, C, ws, nbytes)
     return gfeat
 
 
@@ -1028,16 +854,12 @@ def cd_loss_backward(output, gt, dist1, dist2, idx1, idx2, g_p, g_t, gout=None, 
     _want(gout, _F32, "cd_loss_backward: gout")
     if tuple(gout.shape) != (B, M, 3):
         raise _lib.HouvHipError(f"cd_loss_backward: gout must be [{B},{M},3], got {tuple(gout.shape)}")
-    lib = _lib.load()
-    nbytes = lib.houv_cd_loss_backward_workspace_bytes(B, N, M)
     if workspace is None:
-        workspace = torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=dev)
+        ws = _lib.workspace("houv_cd_loss_backward_workspace_bytes", dev, B, N, M)[0]
+        workspace = ws[:ws.numel() // 4 * 4].view(_I32)     # whole int32 words, whatever size the query names
     _want(workspace, _I32, "cd_loss_backward: workspace")
-    with torch.cuda.device(dev):
-        ok = lib.houv_cd_loss_backward(_lib.ptr(output), _lib.ptr(gt), _lib.ptr(dist1), _lib.ptr(dist2), _lib.ptr(idx1), _lib.ptr(idx2),
-                                       _lib.ptr(g_p), _lib.ptr(g_t), B, N, M, _lib.ptr(gout), _lib.ptr(workspace),
-                                       4 * workspace.numel(), _lib.stream_of(output))
-    _lib.check(ok, "houv_cd_loss_backward")
+    _lib.call("houv_cd_loss_backward", output, output, gt, dist1, dist2, idx1, idx2, g_p, g_t, B, N, M, gout, workspace,
+              4 * workspace.numel())
     return gout
 
 
@@ -1069,17 +891,10 @@ def ef_expand(proj, idx, W2a, W3, b3, r, out=None, want_arg=False):
     _lib.require_gpu(b3); _want(b3, _F32, "ef_expand: b3")
     if tuple(b3.shape) != (O,):
         raise _lib.HouvHipError(f"ef_expand: b3 must be [{O}], got {tuple(b3.shape)}")
-    if out is None:
-        out = torch.empty((B, N * r, O), dtype=_F32, device=proj.device)
     _lib.require_gpu_any(out)
-    if tuple(out.shape) != (B, N * r, O):
-        raise _lib.HouvHipError(f"ef_expand: out must be [{B},{N * r},{O}], got {tuple(out.shape)}")
-    ldo = _rows(out, "ef_expand: out")[3]
+    out, ldo = _out_rows("ef_expand", "out", out, (B, N * r, O), proj.device)
     arg = torch.empty((B, N * r, O), dtype=torch.int8, device=proj.device) if want_arg else None
-    with torch.cuda.device(proj.device):
-        ok = _lib.load().houv_ef_expand(ctypes_ptr(proj), ldp, _lib.ptr(idx), B, N, O, k, r, ctypes_ptr(W2a), ldw, ctypes_ptr(W3),
-                                        _lib.ptr(b3), ctypes_ptr(out), ldo, _lib.ptr(arg), _lib.stream_of(proj))
-    _lib.check(ok, "houv_ef_expand")
+    _lib.call("houv_ef_expand", proj, proj, ldp, idx, B, N, O, k, r, W2a, ldw, W3, b3, out, ldo, arg)
     return (out, arg) if want_arg else out
 
 
@@ -1096,22 +911,13 @@ def ef_expand_backward(proj, idx, arg, W2a, W3, g, r, gproj=None):
     ldg = _rows(g, "ef_expand_backward: g")[3]
     dev = proj.device
     W = 2 * O + 2 * O * r
-    if gproj is None:
-        gproj = torch.empty((B, N, W), dtype=_F32, device=dev)
     _lib.require_gpu_any(gproj)
-    if tuple(gproj.shape) != (B, N, W):
-        raise _lib.HouvHipError(f"ef_expand_backward: gproj must be [{B},{N},{W}], got {tuple(gproj.shape)}")
-    ldgp = _rows(gproj, "ef_expand_backward: gproj")[3]
+    gproj, ldgp = _out_rows("ef_expand_backward", "gproj", gproj, (B, N, W), dev)
     res = {"gproj": gproj, "gW2a": torch.empty((O * r, O), dtype=_F32, device=dev), "gW3": torch.empty((O, O), dtype=_F32, device=dev),
            "gb3": torch.empty((O,), dtype=_F32, device=dev)}
-    lib = _lib.load()
-    nbytes = lib.houv_ef_expand_backward_workspace_bytes(B, N, O, k, r)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=_I32, device=dev)
-    with torch.cuda.device(dev):
-        ok = lib.houv_ef_expand_backward(ctypes_ptr(proj), ldp, _lib.ptr(idx), _lib.ptr(arg), B, N, O, k, r, ctypes_ptr(W2a), ldw,
-                                         ctypes_ptr(W3), ctypes_ptr(g), ldg, ctypes_ptr(gproj), ldgp, _lib.ptr(res["gW2a"]),
-                                         _lib.ptr(res["gW3"]), _lib.ptr(res["gb3"]), _lib.ptr(ws), nbytes, _lib.stream_of(proj))
-    _lib.check(ok, "houv_ef_expand_backward")
+    ws, nbytes = _lib.workspace("houv_ef_expand_backward_workspace_bytes", dev, B, N, O, k, r)
+    _lib.call("houv_ef_expand_backward", proj, proj, ldp, idx, arg, B, N, O, k, r, W2a, ldw, W3, g, ldg, gproj, ldgp, res["gW2a"],
+              res["gW3"], res["gb3"], ws, nbytes)
     return res
 
 
@@ -1251,9 +1057,7 @@ def knn(xyz, k):
         raise _lib.HouvHipError("knn: expected xyz[B,N,3]")
     B, N, _ = xyz.shape
     idx = torch.empty((B, N, k), dtype=_I32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        ok = _lib.load().houv_knn(_lib.ptr(xyz), B, N, int(k), _lib.ptr(idx), _lib.stream_of(xyz))
-    _lib.check(ok, "houv_knn")
+    _lib.call("houv_knn", xyz, xyz, B, N, k, idx)
     return idx
 
 
@@ -1268,10 +1072,7 @@ def edgeconv1(xyz, idx, W, scale, shift):
         raise _lib.HouvHipError("edgeconv1: expected W[64,6], scale[64], shift[64]")
     B, N, k = idx.shape
     out = torch.empty((B * N * k, 64), dtype=_F32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        ok = _lib.load().houv_edgeconv1(_lib.ptr(xyz), _lib.ptr(idx), B, N, k, _lib.ptr(W), _lib.ptr(scale),
-                                        _lib.ptr(shift), _lib.ptr(out), _lib.stream_of(xyz))
-    _lib.check(ok, "houv_edgeconv1")
+    _lib.call("houv_edgeconv1", xyz, xyz, idx, B, N, k, W, scale, shift, out)
     return out
 
 
@@ -1295,15 +1096,7 @@ def max_over_k(act, k, out, col0):
     if not _aligned16(act, view):
         raise _lib.HouvHipError("max_over_k: act and out[:, col0:] must start on 16-byte boundaries (col0 a multiple of 4 "
                                 "in a 16-byte aligned buffer)")
-    with torch.cuda.device(act.device):
-        ok = _lib.load().houv_max_over_k(_lib.ptr(act), npts, int(k), C, ctypes_ptr(view), out.stride(0),
-                                         _lib.stream_of(act))
-    _lib.check(ok, "houv_max_over_k")
-
-
-def ctypes_ptr(t):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr())
+    _lib.call("houv_max_over_k", act, act, npts, k, C, view, out.stride(0))
 
 
 # bench.py sets this to a list to collect (start_event, end_event, flops) per houv_gemm_f32 launch
@@ -1337,13 +1130,8 @@ def gemm(A, B, C=None, *, trans_b=True, alpha=1.0, scale=None, shift=None, resid
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
         ev0.record(torch.cuda.current_stream(A.device))
-    with torch.cuda.device(A.device):
-        ok = _lib.load().houv_gemm_f32(ctypes_ptr(A), ctypes_ptr(B), ctypes_ptr(C), M, N, K, lda, ldb, ldc,
-                                       int(bool(trans_b)), outer, inner, sAo, sAi, sBo, sBi, sCo, sCi, float(alpha),
-                                       _lib.ptr(scale), _lib.ptr(shift),
-                                       None if residual is None else ctypes_ptr(residual), ldr, sRo, sRi,
-                                       int(bool(relu)), _lib.stream_of(A))
-    _lib.check(ok, "houv_gemm_f32")
+    _lib.call("houv_gemm_f32", A, A, B, C, M, N, K, lda, ldb, ldc, bool(trans_b), outer, inner, sAo, sAi, sBo, sBi, sCo, sCi, alpha,
+              scale, shift, residual, ldr, sRo, sRi, bool(relu))
     if GEMM_LOG is not None:
         ev1.record(torch.cuda.current_stream(A.device))
         GEMM_LOG.append((ev0, ev1, 2.0 * outer * inner * M * N * K))
@@ -1370,12 +1158,8 @@ def attention(Q, K, V, scale):
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
         ev0.record(torch.cuda.current_stream(Q.device))
-    with torch.cuda.device(Q.device):
-        ok = _lib.load().houv_attention_f32(ctypes_ptr(Q), ctypes_ptr(K), ctypes_ptr(V), ctypes_ptr(out), P, H, Nq, Nk, dk,
-                                            Q.stride(1), K.stride(1), V.stride(1), out.stride(1), Q.stride(0) if P else 0,
-                                            K.stride(0) if P else 0, V.stride(0) if P else 0, out.stride(0) if P else 0,
-                                            float(scale), _lib.stream_of(Q))
-    _lib.check(ok, "houv_attention_f32")
+    _lib.call("houv_attention_f32", Q, Q, K, V, out, P, H, Nq, Nk, dk, Q.stride(1), K.stride(1), V.stride(1), out.stride(1),
+              Q.stride(0) if P else 0, K.stride(0) if P else 0, V.stride(0) if P else 0, out.stride(0) if P else 0, scale)
     if GEMM_LOG is not None:
         ev1.record(torch.cuda.current_stream(Q.device))
         GEMM_LOG.append((ev0, ev1, 4.0 * P * H * Nq * Nk * dk))
@@ -1396,19 +1180,14 @@ def layernorm(x, a, b, eps=1e-6, residual=None):
         raise _lib.HouvHipError("layernorm: x, a, b and residual must start on 16-byte boundaries")
     rows = x.numel() // D
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_layernorm(_lib.ptr(x), rows, D, _lib.ptr(a), _lib.ptr(b), float(eps), _lib.ptr(residual),
-                                        _lib.ptr(out), _lib.stream_of(x))
-    _lib.check(ok, "houv_layernorm")
+    _lib.call("houv_layernorm", x, x, rows, D, a, b, eps, residual, out)
     return out
 
 
 def softmax_rows_(x):
     _lib.require_gpu(x); _want(x, _F32, "x")
     L = x.shape[-1]
-    with torch.cuda.device(x.device):
-        ok = _lib.load().houv_softmax_rows(_lib.ptr(x), x.numel() // L, L, _lib.stream_of(x))
-    _lib.check(ok, "houv_softmax_rows")
+    _lib.call("houv_softmax_rows", x, x, x.numel() // L, L)
     return x
 
 
@@ -1419,7 +1198,5 @@ def softmax_corr(scores, pts):
         raise _lib.HouvHipError("softmax_corr: expected scores[P,N,M], pts[P,M,3]")
     P, N, M = scores.shape
     corr = torch.empty((P, 3, N), dtype=_F32, device=scores.device)
-    with torch.cuda.device(scores.device):
-        ok = _lib.load().houv_softmax_corr(_lib.ptr(scores), P, N, M, _lib.ptr(pts), _lib.ptr(corr), _lib.stream_of(scores))
-    _lib.check(ok, "houv_softmax_corr")
+    _lib.call("houv_softmax_corr", scores, scores, P, N, M, pts, corr)
     return corr
